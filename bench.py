@@ -8,16 +8,26 @@
                nev = 20, which = :SR, mindim = 20, maxdim = 40, Float64, explicit start vector
     step     : one restart cycle = expand the Krylov basis from k+1 to maxdim, restart to k
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1: launched by torch.distributed.run, one rank per GPU; rows of A and V are block-partitioned
      over the ranks -- total work fixed => "scaling": "strong", as north_star asks.  The per-step
      exchanges have two transports, RCCL and the library's peer-to-peer regions; both are measured
      with the full W + K protocol -- RCCL FIRST and alone, each pass under a watchdog -- and reported
-     under "transports", `value` is the faster valid one.  With 8 ranks (or --config5) the line also
-     carries BASELINE config 5, the 464^3 Laplacian row-partitioned over the ranks, as "config5".)
+     under "transports", `value` is the faster valid one.  With --full and 8 ranks (or --config5) the line
+     also carries BASELINE config 5, the 464^3 Laplacian row-partitioned over the ranks, as "config5".)
 
-The line validates itself: after the timed cycles the reference's two invariants (test/expansion.jl:29-30) are
-evaluated ON THE BENCHED WORKSPACE (`validation`), and a run whose state violates them exits non-zero.
+A plain run sets up, warms up, times the K cycles and prints the line (`roofline` then holds only the figures the
+timed cycles themselves give).  Everything else runs only with --full:
+  * `validation`: after the timed cycles the reference's two invariants (test/expansion.jl:29-30) are evaluated ON
+    THE BENCHED WORKSPACE, and a run whose state violates them exits non-zero;
+  * the per-kernel `roofline` (a second pass of K cycles with HIP events) and `roofline.spmv_plain_csr`;
+  * `shift_invert` (N = 1), `cpu_baseline` (N = 1) and, with 8 ranks, `config5`.
+A `config5` record (--full with 8 ranks, --config5 or KS_BENCH_CONFIG5=1) is always validated the same way.
+
+--dump-outputs DIR writes what the last timed cycle handed its caller as DIR/<name>.npy (float64): the restart's Ritz
+values (`eigenvalues_re`, `eigenvalues_im`), `residuals`, `restart` = (k, nlock, purge), the Krylov-Schur matrix
+`H` = H[0:k+1, 0:k] and, on one rank, the basis columns 0..k at a fixed, seeded sample of rows (`V_rows`, rows listed in
+`V_row_index`).  The inputs depend on the arguments only, so two builds can be compared output for output.
 
 Prints ONE JSON line on rank 0.  `roofline` describes the dominant kernel class (algorithmic bytes per
 launch / HIP-event duration on the library's own stream) and, as `fused_step`, the north-star quantity
@@ -225,9 +235,16 @@ def main():
     ap.add_argument("--sstep", type=int, default=int(os.environ.get("KS_BENCH_SSTEP", "20")),
                     help="s-step (block) expansion: steps per block (ks_workspace_set_sstep; 0 = the per-step expansion of rounds 2-3)")
     ap.add_argument("--config5", action="store_true", help="also measure BASELINE config 5 (464^3 over the ranks) as a second record; "
-                                                           "default: only with 8 ranks")
+                                                           "default: only with --full and 8 ranks")
     ap.add_argument("--config5-grid", type=int, default=464)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: validation of the benched state, the per-kernel HIP-event "
+                         "pass and the plain-CSR SpMV (roofline), the shift-invert record, the CPU baseline, config 5 with 8 ranks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed cycle computed (Ritz values, residuals, H, sampled rows of the basis) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     import torch
 
@@ -297,9 +314,11 @@ def main():
     which = "SR"
     tol = float(np.sqrt(np.finfo(np.float64).eps))
 
-    def measure(transport, m=m, n=n, steps=None, warmup=None, profile=True):
+    def measure(transport, m=m, n=n, steps=None, warmup=None, profile=True, validate=None, dump=True):
         """Build operand + workspace (rows block-partitioned over the ranks), run W untimed and K timed
-        restart cycles, then the same K cycles once more with per-kernel HIP events."""
+        restart cycles, then (--full) the same K cycles once more with per-kernel HIP events.  `validate`: evaluate the
+        invariants on the benched state (default: with --full).  `dump`: keep the last cycle's outputs for --dump-outputs."""
+        validate = args.full if validate is None else validate
         steps = args.steps if steps is None else steps
         warmup = args.warmup if warmup is None else warmup
         if dist is None:
@@ -416,6 +435,7 @@ def main():
                 state.setdefault("cycle_s", []).append(t2 - t0)
                 state["trail"].append((r["k"], r["nlock"]))
                 state["ritz"] = np.sort_complex(r["eigenvalues"][: r["k"]])
+                state["last"] = r
             state["k"], state["active"] = r["k"], r["nlock"]
 
         for _ in range(warmup):
@@ -435,21 +455,24 @@ def main():
         # SELF-VALIDATION on the benched state (outside the timed region): the reference's two invariants of an Arnoldi /
         # Krylov-Schur decomposition, test/expansion.jl:29-30, evaluated on the device for the k columns the last restart
         # left -- ||A V_k - V_{k+1} H_k||_F <= 1e-11 ||H||_F (tol-level instead once vectors are locked: the locked part of
-        # the relation holds to tol |lambda|, src/run.jl:206-208,360) and ||V'V - I||_F <= sqrt(eps) / 100
-        rel, orth = ws.arnoldi_relation(op, state["k"])
-        hnorm = float(np.linalg.norm(ws.H[: state["k"] + 1, : state["k"]]))
-        lim_rel = (1e-11 if state["active"] == 0 else 10.0 * tol) * hnorm
-        lim_orth = float(np.sqrt(np.finfo(np.float64).eps)) / 100.0
-        validation = {"arnoldi_rel": rel / hnorm, "orth": orth, "k": state["k"], "locked": state["active"], "H_fro": hnorm,
-                      "limit_rel": lim_rel / hnorm, "limit_orth": lim_orth, "ok": bool(rel <= lim_rel and orth <= lim_orth),
-                      "what": "||A V_k - V_{k+1} H_k||_F / ||H_k||_F and ||V'V - I||_F of the benched workspace after the timed "
-                              "cycles, evaluated on the device (test/expansion.jl:29-30)"}
-        # Per-kernel HIP-event timing: the event pairs (recorded on the library's own stream around every
+        # the relation holds to tol |lambda|, src/run.jl:206-208,360) and ||V'V - I||_F <= sqrt(eps) / 100  (--full only)
+        validation = None
+        if validate:
+            rel, orth = ws.arnoldi_relation(op, state["k"])
+            hnorm = float(np.linalg.norm(ws.H[: state["k"] + 1, : state["k"]]))
+            lim_rel = (1e-11 if state["active"] == 0 else 10.0 * tol) * hnorm
+            lim_orth = float(np.sqrt(np.finfo(np.float64).eps)) / 100.0
+            validation = {"arnoldi_rel": rel / hnorm, "orth": orth, "k": state["k"], "locked": state["active"], "H_fro": hnorm,
+                          "limit_rel": lim_rel / hnorm, "limit_orth": lim_orth, "ok": bool(rel <= lim_rel and orth <= lim_orth),
+                          "what": "||A V_k - V_{k+1} H_k||_F / ||H_k||_F and ||V'V - I||_F of the benched workspace after the timed "
+                                  "cycles, evaluated on the device (test/expansion.jl:29-30)"}
+        outputs = last_cycle_outputs(ws, state, n, sample_rows=dist is None) if (dump and args.dump_outputs is not None) else None
+        # Per-kernel HIP-event timing (--full): the event pairs (recorded on the library's own stream around every
         # launch) cost ~4 % of throughput on this launch-dense path, so they are NOT left on while `value`
         # is measured; the same K cycles are repeated immediately afterwards with events on and the
         # per-kernel figures of `roofline` come from that second pass (same workload, same state machine).
         prof = None
-        if profile and not args.no_profile:
+        if profile and args.full and not args.no_profile:
             ctx.profile_reset()
             ctx.profile_enable(True)
             for _ in range(steps):
@@ -460,7 +483,7 @@ def main():
         # per-row partial sums"), measured in this run next to the layout the solver picked: the same matrix uploaded
         # as plain CSR (12 B per non-zero), 20 launches on the library's stream between HIP events
         spmv_csr = None
-        if dist is None and profile and not args.no_profile:
+        if dist is None and profile and args.full and not args.no_profile:
             spmv_csr = plain_csr_spmv(pkg, ctx, A_host, n)
         if dist is not None and world > 1:
             t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
@@ -470,7 +493,7 @@ def main():
         op.close()
         ctx.close()
         return dict(elapsed=elapsed, state=state, prof=prof, nnz_global=nnz_global, A_host=A_host, fmt=fmt, placement=placement, basis_passes=basis_passes, sstep=sstep,
-                    validation=validation, spmv_csr=spmv_csr, steps=steps, warmup=warmup)
+                    validation=validation, spmv_csr=spmv_csr, steps=steps, warmup=warmup, outputs=outputs)
 
     # N > 1: the row-partitioned solver has two transports for its per-step exchanges -- RCCL collectives
     # and the library's own peer-to-peer regions over xGMI (csrc/ks_p2p.hpp).  Both are measured with the
@@ -501,7 +524,7 @@ def main():
 
     def build_line(with_cpu_baseline=True):  # (the records gathered so far ride along)
         line = make_line(args, pkg, passes, order, world, rank, force_dist, dict(m=m, n=n, nev=nev, mindim=mindim, maxdim=maxdim, which=which),
-                         with_cpu_baseline)
+                         with_cpu_baseline and args.full)
         line.update(extra)
         return line
 
@@ -568,14 +591,15 @@ def main():
 
     # BASELINE config 5: the 464^3 Laplacian (n = 99 897 344, V = 32.8 GB in total) row-partitioned over the ranks, nev 20,
     # 20/40 -- a second record in the same line, on the transport that won above, 1 untimed + 3 timed cycles
-    if args.config5 or world == 8 or os.environ.get("KS_BENCH_CONFIG5") == "1":
+    if args.config5 or (args.full and world == 8) or os.environ.get("KS_BENCH_CONFIG5") == "1":
         valid = [t for t in order if t in passes and "error" not in passes[t]]
         if valid:
             tr5 = min(valid, key=lambda t: passes[t]["elapsed"])
             g5 = args.config5_grid
             box = {}
             leave_last_words("config5")
-            run_pass(tr5, box, "r", lambda: measure(None if tr5 == "single" else tr5, m=g5, n=g5 ** 3, steps=3, warmup=1, profile=False))
+            run_pass(tr5, box, "r", lambda: measure(None if tr5 == "single" else tr5, m=g5, n=g5 ** 3, steps=3, warmup=1, profile=False,
+                                                validate=True, dump=False))
             r5 = box["r"]
             if "error" in r5:
                 extra["config5"] = {"error": r5["error"], "transport": tr5}
@@ -590,7 +614,7 @@ def main():
                         traffic_fractions(r5["state"]["moved"], r5["state"].get("spec_bytes", 0.0), r5["state"]["t_expand"], r5["state"]["t_restart"], world, HBM_PEAK_GBS)),
                     "validation": r5["validation"],
                 }
-    if world == 1 and not args.no_shift_invert:
+    if world == 1 and args.full and not args.no_shift_invert:
         try:
             # BASELINE config 4's size (n = 5e5) is the record; the n = 5e4 problem of round 3 rides beside it
             extra["shift_invert"] = shift_invert_record(pkg, 500, 1000, reps=10)
@@ -602,6 +626,8 @@ def main():
             extra["shift_invert"] = {"error": f"{type(e).__name__}: {e}"[:300]}
     leave_last_words("cpu baseline / teardown")
     out = build_line()
+    if args.dump_outputs is not None and rank == 0 and out["value"] is not None:
+        write_outputs(args.dump_outputs, passes[out["config"].get("transport", "single")]["outputs"])
     # Tear everything down first and flush the C stdio buffers (RCCL prints a version banner through printf,
     # which sits in the C buffer until exit when stdout is a pipe): the JSON line must be the LAST line on stdout.
     if dist is not None:
@@ -616,10 +642,57 @@ def main():
         except Exception:  # noqa: BLE001
             pass
     emit(out)
+    rc = exit_status(out)
+    if rc:
+        sys.exit(rc)
+
+
+def exit_status(out):
+    """3: no transport survived; 4: a validated state (the headline's with --full, config 5's whenever it ran) violates the
+    Arnoldi relation / orthogonality -- the number is not a valid measurement; 0 otherwise.  A record without a validation
+    (a plain run) or with an error instead of a measurement does not fail here."""
     if out["value"] is None:
-        sys.exit(3)
-    if not out.get("validation", {}).get("ok", True) or not (out.get("config5") or {}).get("validation", {}).get("ok", True):
-        sys.exit(4)  # the benched state violates the Arnoldi relation / orthogonality: the number is not a valid measurement
+        return 3
+    for rec in (out, out.get("config5") or {}):
+        if not (rec.get("validation") or {}).get("ok", True):
+            return 4
+    return 0
+
+
+DUMP_SAMPLE_ROWS = 1 << 16      # rows of the basis written by --dump-outputs (all of them when n is smaller)
+DUMP_SAMPLE_SEED = 20240917
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def last_cycle_outputs(ws, state, n, sample_rows=True):
+    """What the last timed cycle (ks_expand_restart) handed its caller, as float64 arrays: the restart's return values, the
+    Krylov-Schur matrix H[0:k+1, 0:k] and -- with the whole basis on this rank -- its columns 0..k at a fixed, seeded
+    sample of rows.  Outside the timed region.  Downloading a column applies a pending restart rotation first; with --full the
+    validation before it has done so already (ks_arnoldi_relation), so the HIP-event pass that follows starts from the same
+    state with or without a dump.  Whole columns are downloaded (k + 1 <= maxdim transfers of 8 n bytes, a fraction of a
+    second at the headline size): a device-side gather would need ks_workspace_col_ptr, which ends the library's provenance of the basis."""
+    r, k = state["last"], state["k"]
+    out = {"eigenvalues_re": np.ascontiguousarray(r["eigenvalues"].real, dtype=np.float64),
+           "eigenvalues_im": np.ascontiguousarray(r["eigenvalues"].imag, dtype=np.float64),
+           "residuals": np.asarray(r["residuals"], dtype=np.float64).copy(),
+           "restart": np.array([r["k"], r["nlock"], r["purge"]], dtype=np.float64)}
+    if sample_rows:
+        rows = np.arange(n) if n <= DUMP_SAMPLE_ROWS else \
+            np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, DUMP_SAMPLE_ROWS, replace=False))
+        out["V_rows"] = np.stack([ws.col(j)[rows] for j in range(k + 1)], axis=1).astype(np.float64)
+        out["V_row_index"] = rows.astype(np.float64)
+    out["H"] = np.array(ws.H[: k + 1, :k], dtype=np.float64)
+    return out
+
+
+def write_outputs(path, outputs):
+    """--dump-outputs: one DIR/<name>.npy per array, at most DUMP_LIMIT_BYTES in all."""
+    total = sum(a.nbytes for a in outputs.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def spec_chain_products(nst, cap=10):

@@ -142,3 +142,51 @@ def test_traffic_fractions_book_speculative_products_to_the_interval_they_ran_in
     assert fs["moved_frac"] == fs["cycle_frac"] == st["moved"] / (st["t_expand"] + st["t_restart"]) / 1e9 / 8000.0
     assert fs["expand_interval_frac"] == (st["moved"] - 100 * spmv_b) / st["t_expand"] / 1e9 / 8000.0
     assert fs["spec_products"] == 100 and "WHOLE cycle time" in fs["what"]
+
+
+def test_dump_outputs_hold_the_last_cycle_in_float64_within_the_limit(tmp_path):
+    """--dump-outputs: the last timed cycle's return values, H[0:k+1, 0:k] and the basis columns 0..k at a fixed, seeded
+    sample of rows (the same rows every run), float64, at most 64 MB in all -- also at the headline size with k = maxdim - 1."""
+    n, maxdim, k = 216 ** 3, 40, 39
+
+    class _Ws:
+        H = np.arange((maxdim + 1) * maxdim, dtype=np.float64).reshape(maxdim + 1, maxdim)
+
+        def col(self, j):     # row-dependent: the sample must come from the rows it lists
+            return np.arange(n, dtype=np.float64) + 1e7 * j
+
+    lams = np.arange(maxdim) + 0.5j
+    state = dict(k=k, last=dict(k=k, nlock=3, purge=0, eigenvalues=lams, residuals=np.ones(maxdim)))
+    out = bench.last_cycle_outputs(_Ws(), state, n)
+    assert out["H"].shape == (k + 1, k) and (out["H"] == _Ws.H[: k + 1, :k]).all()
+    assert (out["eigenvalues_re"] == lams.real).all() and (out["eigenvalues_im"] == 0.5).all() and list(out["restart"]) == [k, 3, 0]
+    assert out["V_rows"].shape == (bench.DUMP_SAMPLE_ROWS, k + 1)
+    rows = out["V_row_index"]
+    assert len(np.unique(rows)) == len(rows) and rows.max() < n and (np.diff(rows) > 0).all()
+    for j in range(k + 1):
+        assert (out["V_rows"][:, j] == rows + 1e7 * j).all(), j
+    small = bench.last_cycle_outputs(_Ws(), dict(state, k=k), 1000)   # n below the sample size: every row, in order
+    assert (small["V_row_index"] == np.arange(1000)).all() and (small["V_rows"][:, 3] == np.arange(1000) + 3e7).all()
+    assert (bench.last_cycle_outputs(_Ws(), state, n)["V_row_index"] == rows).all()
+    assert "V_rows" not in bench.last_cycle_outputs(_Ws(), state, n, sample_rows=False)
+    bench.write_outputs(str(tmp_path / "d"), out)
+    files = sorted(p.name for p in (tmp_path / "d").iterdir())
+    assert files == sorted(name + ".npy" for name in out)
+    assert sum((tmp_path / "d" / f).stat().st_size for f in files) <= 64 << 20
+    assert all(np.load(tmp_path / "d" / f).dtype == np.float64 for f in files)
+
+
+def test_exit_status_fails_only_a_validated_state_that_violates_the_invariants():
+    """A plain run carries no `validation`; a config-5 record (--config5 without --full included) carries its own.  Only
+    a validation that failed -- of the headline or of config 5 -- makes the run exit 4; a record without one, or with an
+    error instead of a measurement, does not."""
+    ok, bad = dict(ok=True), dict(ok=False)
+    assert bench.exit_status(dict(value=None)) == 3
+    assert bench.exit_status(dict(value=1.0)) == 0
+    assert bench.exit_status(dict(value=1.0, validation=ok, config5=dict(validation=ok))) == 0
+    assert bench.exit_status(dict(value=1.0, config5=dict(value=2.0, validation=ok))) == 0
+    assert bench.exit_status(dict(value=1.0, config5=dict(value=2.0, validation=None))) == 0
+    assert bench.exit_status(dict(value=1.0, config5=dict(error="CommTimeout", transport="p2p"))) == 0
+    assert bench.exit_status(dict(value=1.0, config5=None)) == 0
+    assert bench.exit_status(dict(value=1.0, validation=bad)) == 4
+    assert bench.exit_status(dict(value=1.0, config5=dict(value=2.0, validation=bad))) == 4

@@ -7,13 +7,14 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 
-def _bench(extra_env, nproc=2, grid=64, timeout=420, extra_args=()):
+def _bench(extra_env, nproc=2, grid=64, timeout=420, extra_args=(), full=False):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
@@ -21,7 +22,7 @@ def _bench(extra_env, nproc=2, grid=64, timeout=420, extra_args=()):
     env.update(extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "3", "--warmup", "1",
-           "--grid", str(grid), *extra_args]
+           "--grid", str(grid), *(("--full",) if full else ()), *extra_args]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:] + r.stderr[-2000:]
@@ -29,7 +30,7 @@ def _bench(extra_env, nproc=2, grid=64, timeout=420, extra_args=()):
 
 
 def test_both_transports_measured_and_agree():
-    r, d = _bench({})
+    r, d = _bench({}, full=True)
     assert r.returncode == 0
     assert set(d["transports"]) == {"p2p", "host"} and all("value" in v for v in d["transports"].values()), d["transports"]
     assert d["value"] == max(v["value"] for v in d["transports"].values()) and d["n_gpus"] == 2
@@ -41,18 +42,24 @@ def test_both_transports_measured_and_agree():
     assert v["ok"] and v["arnoldi_rel"] <= v["limit_rel"] and v["orth"] <= v["limit_orth"], v
 
 
-def test_config5_record_rides_in_the_same_line():
-    """BASELINE config 5 (464^3 over the ranks) as a second record of the N > 1 line -- here at 48^3 over 2 ranks on one GPU."""
-    r, d = _bench({}, extra_args=("--config5", "--config5-grid", "48"))
+def test_config5_record_rides_in_the_same_line(tmp_path):
+    """BASELINE config 5 (464^3 over the ranks) as a second record of the N > 1 line -- here at 48^3 over 2 ranks on one GPU.
+    Asked for with --config5 alone (no --full): the headline carries no validation, config 5 its own; --dump-outputs with
+    several ranks writes the replicated results of the winning transport's last cycle (no basis rows)."""
+    r, d = _bench({}, extra_args=("--config5", "--config5-grid", "48", "--dump-outputs", str(tmp_path / "d")))
     assert r.returncode == 0, r.stderr[-2000:]
     c5 = d["config5"]
     assert c5["n_gpus"] == 2 and c5["value"] > 0 and c5["steps"] == 3 and "48^3" in c5["workload"]
     assert c5["transport"] == d["config"]["transport"] and c5["validation"]["ok"], c5
-    assert d["value"] > 0 and "64^3" in d["config"]["workload"]
+    assert d["value"] > 0 and "64^3" in d["config"]["workload"] and "validation" not in d
+    dump = {p.stem: np.load(p) for p in (tmp_path / "d").glob("*.npy")}
+    assert set(dump) == {"eigenvalues_re", "eigenvalues_im", "residuals", "restart", "H"}, set(dump)
+    k = int(dump["restart"][0])
+    assert dump["H"].shape == (k + 1, k) and all(x.dtype == np.float64 and np.isfinite(x).all() for x in dump.values())
 
 
 def test_single_gpu_line_validates_itself_and_reports_the_plain_csr_spmv():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--grid", "96", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--grid", "96", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=420)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, r.stdout[-2000:] + r.stderr[-2000:]
@@ -65,6 +72,36 @@ def test_single_gpu_line_validates_itself_and_reports_the_plain_csr_spmv():
     # the side record of the sparse shift-invert operator (BASELINE config 4 in its general form), measured in the run
     si = d["shift_invert"]
     assert si["measured_in_run"] and si["repeatable"] and si["max_rel_diff_vs_host_solve"] < 1e-11 and 0.0 < si["ms_per_product"] < si["host_solve_ms"], si
+
+
+def test_plain_single_gpu_run_is_lean_and_dumps_the_last_cycle(tmp_path):
+    """Without --full the line carries the headline only (no validation, per-kernel pass, side records or CPU baseline);
+    --dump-outputs writes the last timed cycle's results, and two runs with the same arguments write the same ones (to 1e-9)."""
+    dumps = []
+    for i in range(2):
+        d_out = tmp_path / f"run{i}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--grid", "40",
+               "--dump-outputs", str(d_out)]
+        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert r.returncode == 0 and len(lines) == 1, r.stdout[-2000:] + r.stderr[-2000:]
+        d = json.loads(lines[0])
+        assert d["value"] > 0 and d["steps"] == 4 and d["warmup"] == 1 and d["unit"] == "iters/s" and d["dtype"] == "f64"
+        assert abs(d["ms_per_step"] - 1e3 * d["config"]["arnoldi_iterations_timed"] / d["value"] / 4) < 1e-6 * d["ms_per_step"]
+        for k in ("validation", "cpu_baseline", "shift_invert", "config5"):
+            assert k not in d, k
+        assert "per_class" not in d["roofline"] and "spmv_plain_csr" not in d["roofline"]
+        dumps.append({p.stem: np.load(p) for p in d_out.glob("*.npy")})
+    a, b = dumps
+    assert set(a) == {"eigenvalues_re", "eigenvalues_im", "residuals", "restart", "H", "V_rows", "V_row_index"}, set(a)
+    assert all(x.dtype == np.float64 and np.isfinite(x).all() for x in a.values())
+    k = int(a["restart"][0])
+    assert a["H"].shape == (k + 1, k) and a["V_rows"].shape == (40 ** 3, k + 1) and (a["V_row_index"] == np.arange(40 ** 3)).all()
+    # the first k + 1 columns of the basis are orthonormal (all rows are in the sample at this size)
+    assert np.linalg.norm(a["V_rows"].T @ a["V_rows"] - np.eye(k + 1)) < 1.5e-10
+    assert (a["restart"] == b["restart"]).all()
+    for name in a:
+        assert np.allclose(a[name], b[name], rtol=1e-9, atol=1e-9 * max(1.0, float(np.abs(a[name]).max()))), name
 
 
 @pytest.mark.parametrize("victim,survivor", [("host", "p2p"), ("p2p", "host")])
@@ -101,7 +138,7 @@ def test_eight_ranks_end_to_end_on_one_device():
     line with all eight ranks on device 0 (peer-to-peer and host-staged transports; RCCL refuses eight ranks on one device), the
     default block expansion, config 5's record riding along.  Asserted: ONE well-formed line, n_gpus 8, every rank's share in
     the validation, the roofline block and both transports present."""
-    r, d = _bench({}, nproc=8, grid=64, timeout=900, extra_args=("--config5", "--config5-grid", "48"))
+    r, d = _bench({}, nproc=8, grid=64, timeout=900, extra_args=("--config5", "--config5-grid", "48"), full=True)
     assert r.returncode == 0, r.stderr[-3000:]
     assert d["n_gpus"] == 8 and d["value"] > 0 and d["steps"] == 3 and d["scaling"] == "strong" and d["config"]["parallelism"] == "rows/8"
     # the collective-structured (host-staged) pass must succeed.  The peer-to-peer pass spins inside kernels for its peers:

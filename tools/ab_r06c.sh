@@ -15,5 +15,5 @@ for c in cfg3 cfg2 cfg4; do
     KS_QSTAGE_EVENT=$ev KS_TRUE_START=$ts python tools/config_bench.py $c --sstep 20 --steps 20 2>/dev/null | one "$c event=$ev true_start=$ts"
   done; done
 done
-for ev in 1 0; do KS_QSTAGE_EVENT=$ev python bench.py --no-cpu-baseline --no-shift-invert --steps 20 2>/dev/null | one "headline event=$ev"; done
+for ev in 1 0; do KS_QSTAGE_EVENT=$ev python bench.py --full --no-cpu-baseline --no-shift-invert --steps 20 2>/dev/null | one "headline event=$ev"; done
 done

@@ -3,7 +3,7 @@
 # "ENV1=a ENV2=b"), prints iterations/s and the per-class average launch times (us).
 #   gpurun -- 'bash tools/bench_ab.sh KS_SPMV_FORMAT=csr KS_SPMV_FORMAT=dvi'
 for v in "$@"; do
-  env $v python bench.py --steps 10 --warmup 2 --no-cpu-baseline > /tmp/b.json 2>/dev/null
+  env $v python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > /tmp/b.json 2>/dev/null
   python - "$v" <<PY
 import json,sys
 d=json.load(open("/tmp/b.json")); pc=d["roofline"]["per_class"]

@@ -19,9 +19,9 @@ for x in r:
     w.writerow([x["Dispatch_Id"], x["Kernel_Name"], x["Counter_Name"], x["Counter_Value"]])
 PY
 }
-python $REPO/bench.py > $OUT/bench.json 2> $OUT/bench.err
-KS_PLACE_TRIALS=2 KS_PLACE_CONTIGUOUS=1 python $REPO/bench.py --no-cpu-baseline > $OUT/bench_placement_contiguous.json 2>> $OUT/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python $REPO/bench.py --no-cpu-baseline > $OUT/bench_under_rocprof.json 2>> $OUT/bench.err
+python $REPO/bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+KS_PLACE_TRIALS=2 KS_PLACE_CONTIGUOUS=1 python $REPO/bench.py --full --no-cpu-baseline > $OUT/bench_placement_contiguous.json 2>> $OUT/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python $REPO/bench.py --full --no-cpu-baseline > $OUT/bench_under_rocprof.json 2>> $OUT/bench.err
 cp "$(find /tmp/kt -name '*kernel_stats.csv' | head -1)" $OUT/kernel_stats.csv
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --kernel-trace --pmc $c --output-format csv -d /tmp/pmc_$c -- python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-profile > /dev/null 2>> $OUT/bench.err
@@ -52,7 +52,7 @@ python tools/cb_single_ab.py 1000000 2000000 10000000 2>&1 | grep -v "^RCCL\|^HI
 # (c) rotation kernels A/B on the headline
 for rot in fma mfma; do
   echo "KS_ROTATE=$rot" >> $OUT/rotation.txt
-  KS_ROTATE=$rot python bench.py --no-cpu-baseline --steps 10 --warmup 2 2>/dev/null | python -c "
+  KS_ROTATE=$rot python bench.py --full --no-cpu-baseline --steps 10 --warmup 2 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('  iterations/s', round(d['value'],1), ' rotate', d['roofline']['per_class']['rotate'])" >> $OUT/rotation.txt

@@ -28,12 +28,12 @@ for x in r:
     w.writerow([x["Dispatch_Id"], x["Kernel_Name"], x["Counter_Name"], x["Counter_Value"]])
 PY
 }
-python $REPO/bench.py > $OUT/bench.json 2> $OUT/bench.err; check $OUT/bench.err
-python $REPO/bench.py --no-cpu-baseline --no-shift-invert --sstep 0 > $OUT/bench_sstep0.json 2>> $OUT/bench.err
-python $REPO/bench.py --no-cpu-baseline --no-shift-invert --sstep 5 > $OUT/bench_sstep5.json 2>> $OUT/bench.err
-python $REPO/bench.py --no-cpu-baseline --no-shift-invert --sstep 8 > $OUT/bench_sstep8.json 2>> $OUT/bench.err
-python $REPO/bench.py --no-cpu-baseline --no-shift-invert --sstep 10 > $OUT/bench_sstep10.json 2>> $OUT/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python $REPO/bench.py --no-cpu-baseline --no-shift-invert > $OUT/bench_under_rocprof.json 2>> $OUT/bench.err
+python $REPO/bench.py --full > $OUT/bench.json 2> $OUT/bench.err; check $OUT/bench.err
+python $REPO/bench.py --full --no-cpu-baseline --no-shift-invert --sstep 0 > $OUT/bench_sstep0.json 2>> $OUT/bench.err
+python $REPO/bench.py --full --no-cpu-baseline --no-shift-invert --sstep 5 > $OUT/bench_sstep5.json 2>> $OUT/bench.err
+python $REPO/bench.py --full --no-cpu-baseline --no-shift-invert --sstep 8 > $OUT/bench_sstep8.json 2>> $OUT/bench.err
+python $REPO/bench.py --full --no-cpu-baseline --no-shift-invert --sstep 10 > $OUT/bench_sstep10.json 2>> $OUT/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python $REPO/bench.py --full --no-cpu-baseline --no-shift-invert > $OUT/bench_under_rocprof.json 2>> $OUT/bench.err
 cp "$(find /tmp/kt -name '*kernel_stats.csv' | head -1)" $OUT/kernel_stats.csv
 N=10077696; NNZ=70263936
 rm -f $OUT/pmc_traffic.json

@@ -31,8 +31,8 @@ for x in r:
     w.writerow([x["Dispatch_Id"], x["Kernel_Name"], x["Counter_Name"], x["Counter_Value"]])
 PY
 }
-B="python $REPO/bench.py --no-cpu-baseline --no-shift-invert"
-python $REPO/bench.py --steps 20 > $OUT/bench.json 2> $OUT/bench.err; check $OUT/bench.err
+B="python $REPO/bench.py --full --no-cpu-baseline --no-shift-invert"
+python $REPO/bench.py --full --steps 20 > $OUT/bench.json 2> $OUT/bench.err; check $OUT/bench.err
 KS_ROT_DEFER=0 KS_SPEC_CHAIN=0 $B --steps 20 > $OUT/bench_plain_sequence.json 2>> $OUT/bench.err
 KS_ROT_DEFER=0 KS_SPEC_CHAIN=0 KS_BLK_MFMA=0 $B --steps 20 > $OUT/bench_ring_kernels.json 2>> $OUT/bench.err
 $B --sstep 0 > $OUT/bench_sstep0.json 2>> $OUT/bench.err

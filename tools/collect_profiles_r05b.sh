@@ -13,8 +13,8 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/prof5b
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python $REPO/bench.py --no-cpu-baseline --no-shift-invert"
-python $REPO/bench.py --steps 20 > $OUT/bench.json 2> $OUT/bench.err
+B="python $REPO/bench.py --full --no-cpu-baseline --no-shift-invert"
+python $REPO/bench.py --full --steps 20 > $OUT/bench.json 2> $OUT/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- $B --steps 20 > $OUT/bench_under_rocprof.json 2>> $OUT/bench.err
 cp "$(find /tmp/kt -name '*kernel_stats.csv' | head -1)" $OUT/kernel_stats.csv
 for cfg in cfg2 cfg3 cfg4; do

@@ -30,8 +30,8 @@ for x in r:
     w.writerow([x["Dispatch_Id"], x["Kernel_Name"], x["Counter_Name"], x["Counter_Value"]])
 PY
 }
-B="python $REPO/bench.py --no-cpu-baseline --no-shift-invert"
-python $REPO/bench.py --steps 20 > $OUT/bench.json 2> $OUT/bench.err; check $OUT/bench.err
+B="python $REPO/bench.py --full --no-cpu-baseline --no-shift-invert"
+python $REPO/bench.py --full --steps 20 > $OUT/bench.json 2> $OUT/bench.err; check $OUT/bench.err
 KS_STENCIL_MARCH=0 $B --steps 20 > $OUT/bench_stencil2.json 2>> $OUT/bench.err
 KS_MARCH_WINDOW=0 $B --steps 20 > $OUT/bench_march_registers.json 2>> $OUT/bench.err
 $B --sstep 0 > $OUT/bench_sstep0.json 2>> $OUT/bench.err

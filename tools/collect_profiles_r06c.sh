@@ -27,8 +27,8 @@ for x in r:
     w.writerow([x["Dispatch_Id"], x["Kernel_Name"], x["Counter_Name"], x["Counter_Value"]])
 PY
 }
-B="python $REPO/bench.py --no-cpu-baseline --no-shift-invert"
-python $REPO/bench.py --steps 20 > $OUT/bench.json 2> $OUT/bench.err
+B="python $REPO/bench.py --full --no-cpu-baseline --no-shift-invert"
+python $REPO/bench.py --full --steps 20 > $OUT/bench.json 2> $OUT/bench.err
 $B --steps 20 --sync-cycles > $OUT/bench_sync_cycles.json 2>> $OUT/bench.err
 KS_QSTAGE_EVENT=0 $B --steps 20 > $OUT/bench_stream_sync.json 2>> $OUT/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- $B --steps 20 > $OUT/bench_under_rocprof.json 2>> $OUT/bench.err

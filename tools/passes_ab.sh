@@ -9,7 +9,7 @@ print('$1', 'value %.1f' % d.get('value', d.get('iters_per_s', 0)), '| dominant'
       '| expand %.4f s restart %.4f s' % (f['expand_seconds'], f['restart_seconds']), '| per class', {k: round(v['GBps']) for k, v in r.get('per_class', {}).items() if v.get('GBps')})
 "; }
 for rep in 1 2; do for p in 3 2; do
-  KS_PASSES=$p python bench.py --no-cpu-baseline 2>/dev/null | line "headline KS_PASSES=$p:"
+  KS_PASSES=$p python bench.py --full --no-cpu-baseline 2>/dev/null | line "headline KS_PASSES=$p:"
 done; done
 for cfg in cfg2 cfg3 cfg4big; do for p in 3 2; do
   KS_PASSES=$p python tools/config_bench.py $cfg 2>/dev/null | python -c "

@@ -2,7 +2,7 @@
 # write-back staging depth of the projection kernel: KS_FUSED_WB=8 (32 KiB bursts, 2 workgroups / CU) vs 24 (96 KiB bursts, 1 / CU; default)
 cd $GRAFT_REPO_ROOT
 for rep in 1 2; do for wb in 8 24; do
-  KS_FUSED_WB=$wb python bench.py --no-cpu-baseline 2>/dev/null | python -c "
+  KS_FUSED_WB=$wb python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d['roofline']
 print('headline WB=$wb:', 'value %.1f' % d['value'], 'dominant %s frac %.3f' % (r['kernel'][:16], r['frac']), 'moved_frac %.3f' % r['fused_step']['moved_frac'], {k: round(v['GBps']) for k, v in r['per_class'].items() if v.get('GBps')})"
