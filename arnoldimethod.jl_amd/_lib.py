@@ -17,6 +17,8 @@ KS_F64, KS_C64 = 0, 1
 KS_I32, KS_I64 = 0, 1
 KS_CSR, KS_CSC = 0, 1
 LAYOUTS = {-1: "none", 0: "csr", 1: "csr-vi", 2: "csr-dvi", 3: "sell", 4: "sell-vi", 5: "stencil", 6: "csr-cb"}
+PLAN_FACTS = ("ptr64", "ni", "nblk", "nlong", "row_gather", "nslices", "sell_entries", "ncolblocks", "cb_rpt", "cb_ni", "nstencil",
+              "nstencil_local", "stencil_mask_bytes", "ndvi", "dvi_unroll")  # KS_PLAN_* of include/kschur.h
 WHICH = {"LM": 0, "LR": 1, "SR": 2, "LI": 3, "SI": 4}
 
 
@@ -144,6 +146,7 @@ PROTOTYPES = {
     "ks_host_restart_step": [i32, vp, i32, vp, i32, i32, i32, i32, i32, dbl, i32, P(C.c_int), P(C.c_int), P(C.c_int), vp, vp, vp],
     "ks_host_sortschur": [i32, vp, i32, i32, i32, vp, i32, i32, i32, i32],
     "ks_host_givens": [i32, vp, vp, P(dbl), vp, vp],
+    "ks_host_csr_plan": [i64, i64, i64, vp, vp, vp, i32, i32, i32, i32, i32, i64, i64, P(C.c_int), P(C.c_int), P(dbl), P(dbl), vp, vp, vp, vp, i64, vp, i32],
     "ks_last_words": [C.c_char_p, i32],
 }
 

@@ -9,12 +9,7 @@
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-thread_local std::string g_last_error;
-
-struct KsError {
-  int code;
-  std::string msg;
-};
+thread_local std::string g_last_error;  // (KsError, KS_REQUIRE, round_up, env_int: ks_host_defs.hpp)
 
 #define KS_HIP(expr)                                                                              \
   do {                                                                                            \
@@ -30,11 +25,6 @@ struct KsError {
     if (r__ != ncclSuccess)                                                                         \
       throw KsError{KS_ERR_RCCL, std::string(#expr) + " failed: " + ncclGetErrorString(r__) + " (" + \
                                      __FILE__ + ":" + std::to_string(__LINE__) + ")"};              \
-  } while (0)
-
-#define KS_REQUIRE(cond, code, text)           \
-  do {                                         \
-    if (!(cond)) throw KsError{(code), (text)}; \
   } while (0)
 
 template <class F> int guarded(F&& f) {
@@ -62,12 +52,6 @@ template <> struct DevT<cplx> { using type = cd; };
 template <class D> struct HostT;
 template <> struct HostT<double> { using type = double; };
 template <> struct HostT<cd> { using type = cplx; };
-
-inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
-inline int env_int(const char* name, int dflt) {
-  const char* s = std::getenv(name);
-  return s ? std::atoi(s) : dflt;
-}
 
 }  // namespace
 

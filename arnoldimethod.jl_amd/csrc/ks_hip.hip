@@ -36,6 +36,7 @@ using ksd::DevState;
 using ksd::kBlock;
 
 #include "ks_context.hpp"    // errors, ks_ctx, transports
+#include "ks_csr_layout.hpp" // host-only: which layout a stored matrix gets, and its host arrays
 #include "ks_operators.hpp"  // ks_operator and its layouts
 #include "ks_sptrsv.hpp"     // shift-invert operator from triangular factors (sparse triangular solves)
 #include "ks_workspace.hpp"  // ks_workspace, launch helpers, expansion, rotations
@@ -211,7 +212,7 @@ int ks_operator_csr(ks_ctx* ctx, int64_t nrows_local, int64_t ncols, int64_t nnz
       using D = typename DevT<T>::type;
       std::vector<D> vv;
       build_csr_host<D>(nrows_local, ncols, nnz, ptr, idx, val, layout, index_base, index_type, rp, ci, vv);
-      *out = make_csr<D>(ctx, nrows_local, nnz, rp, ci, vv, /*cb_mode=*/(ctx->nranks == 1 && nrows_local == ncols) ? 1 : 0);
+      *out = make_csr<D>(ctx, nrows_local, nnz, rp, ci, vv, (ctx->nranks == 1 && nrows_local == ncols) ? CbMode::Allowed : CbMode::None);
     });
   });
 }
@@ -250,7 +251,7 @@ int ks_operator_csr_dist(ks_ctx* ctx, int64_t nrows_local, int64_t nghost, int64
         }
         if (!ok) nlow = -1;
       }
-      CsrOp<D>* op = make_csr<D>(ctx, nrows_local, nnz, rp, ci, vv, nlow >= 0 ? 3 : 0, nghost, std::max<int64_t>(nlow, 0));
+      CsrOp<D>* op = make_csr<D>(ctx, nrows_local, nnz, rp, ci, vv, nlow >= 0 ? CbMode::DistributedRowBlock : CbMode::None, nghost, std::max<int64_t>(nlow, 0));
       std::unique_ptr<CsrOp<D>> guard(op);
       op->nghost = nghost;
       op->p2p_halo = ctx->p2p.attached;
@@ -1376,6 +1377,44 @@ int ks_arnoldi_relation(ks_operator* A, ks_workspace* ws, int k, double* resid, 
 }
 
 // ---- host small dense exports (no device needed) ----------------------------------------------------------
+int ks_host_csr_plan(int64_t nrows_local, int64_t ncols, int64_t nnz, const void* ptr, const void* idx, const void* val, int layout,
+                     int index_base, int index_type, int dtype, int num_cu, int64_t nghost, int64_t nlow, int* plan_layout, int* ndict,
+                     double* bytes_per_nnz, double* aux_bytes, int64_t* facts, int32_t* stencil_delta, int64_t* blkrow, int64_t* blkptr,
+                     int64_t blk_cap, int64_t* cb_bounds, int cb_cap) {
+  return guarded([&] {
+    KS_REQUIRE(nrows_local >= 0 && ncols >= 0 && nnz >= 0, KS_ERR_ARGUMENT, "negative size");
+    KS_REQUIRE(layout == KS_CSR || layout == KS_CSC, KS_ERR_ARGUMENT, "bad layout");
+    KS_REQUIRE(index_type == KS_I32 || index_type == KS_I64, KS_ERR_ARGUMENT, "bad index type");
+    KS_REQUIRE(nghost < 0 || ncols == nrows_local + nghost, KS_ERR_DIMENSION, "a distributed row block has nrows_local + nghost columns");
+    // what ks_operator_csr (one GPU) and ks_operator_csr_dist hand to make_csr
+    const CbMode mode = nghost < 0 ? (nrows_local == ncols ? CbMode::Allowed : CbMode::None) : (nlow >= 0 ? CbMode::DistributedRowBlock : CbMode::None);
+    std::vector<int64_t> rp;
+    std::vector<int32_t> ci;
+    dispatch_dtype(dtype, [&](auto tag) {
+      using D = typename DevT<decltype(tag)>::type;
+      std::vector<D> vv;
+      build_csr_host<D>(nrows_local, ncols, nnz, ptr, idx, val, layout, index_base, index_type, rp, ci, vv);
+      const CsrPlan<D> P = plan_csr<D>(CsrHost<D>{nrows_local, nnz, rp, ci, vv}, FormatRequest::from_env(), mode, std::max<int64_t>(nghost, 0),
+                                       std::max<int64_t>(nlow, 0), num_cu);
+      if (plan_layout) *plan_layout = P.layout;
+      if (ndict) *ndict = P.nstencil > 0 ? P.nstencil : P.ndvi > 0 ? P.ndvi : P.ndict;
+      if (bytes_per_nnz) *bytes_per_nnz = P.bytes_per_nnz;
+      if (aux_bytes) *aux_bytes = P.aux_bytes;
+      if (facts) {
+        const int64_t f[KS_PLAN_NFACTS] = {P.ptr64, P.ni, P.nblk, P.nlong, P.row_gather, P.nslices, P.sell_entries, (int64_t)P.cblocks.size(),
+                                           P.cb_rpt, P.cb_ni, P.nstencil, P.nstencil_local, P.stencil_mask_bytes, P.ndvi, P.dvi_unroll};
+        std::copy(f, f + KS_PLAN_NFACTS, facts);
+      }
+      if (stencil_delta) std::copy(P.sdelta.begin(), P.sdelta.end(), stencil_delta);
+      for (int64_t b = 0; b <= P.nblk && b < blk_cap && !P.blkrow.empty(); ++b) {
+        if (blkrow) blkrow[b] = P.blkrow[b];
+        if (blkptr) blkptr[b] = P.blkptr[b];
+      }
+      for (int b = 0; cb_bounds && b < (int)P.cb_bounds.size() && b < cb_cap; ++b) cb_bounds[b] = P.cb_bounds[b];
+    });
+  });
+}
+
 int ks_host_schurfact(int dtype, void* H, int m, int n, int ldh, int start, int to, void* Q, int nq, int ldq) {
   return guarded([&] {
     KS_REQUIRE(H, KS_ERR_ARGUMENT, "null H");

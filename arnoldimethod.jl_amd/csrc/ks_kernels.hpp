@@ -18,6 +18,7 @@
 
 #include <type_traits>
 
+#include "ks_host_defs.hpp"  // kBlock and the SpMV launch-shape constants (shared with the host-only layout planning)
 #include "ks_p2p.hpp"
 
 namespace ksd {
@@ -26,7 +27,6 @@ struct cd {
   double x, y;
 };
 
-constexpr int kBlock = 256;           // threads per workgroup (4 waves)
 constexpr double kEta = 0.70710678118654752440;  // sqrt(2)/2, src/expansion.jl:32,74
 
 // Per-workspace device state shared by the kernels of one expansion batch.
@@ -238,9 +238,6 @@ __device__ __forceinline__ cd shift_apply(const ShiftArg<cd>& sh, cd s, const cd
   return cd{(s.x - tx.x) * sh.sigma, (s.y - tx.y) * sh.sigma};
 }
 
-constexpr int kSpmvRows = 256;       // rows per block at most
-constexpr int kSpmvCapBytes = 32768;  // LDS for the products of a block: NI * 256 * sizeof(T) <= 32 KiB
-
 __device__ __forceinline__ int xcd_remap(int b, int nt) {
   const int q = nt >> 3, r = nt & 7, xcd = b & 7;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
@@ -450,7 +447,6 @@ __global__ void __launch_bounds__(kBlock)
 // together and stay in step without any global synchronisation).  Replaces one launch per block with the row sums
 // written to and read back from y in between (16 n bytes per block boundary, and a launch each: 46.5 us at n = 1e6).
 // ------------------------------------------------------------------------------------------------
-constexpr int kCbMaxBlocks = 8;
 template <class T> struct CbArgs {
   int nb;
   const int32_t* rowptr[kCbMaxBlocks];
@@ -704,7 +700,6 @@ __device__ __forceinline__ double sub_s(double a, double b) { return a - b; }
 __device__ __forceinline__ cd sub_s(cd a, cd b) { return cd{a.x - b.x, a.y - b.y}; }
 __device__ __forceinline__ double scl(double a, double s);
 __device__ __forceinline__ cd scl(cd a, double s);
-constexpr int kStencilSlots = 32;
 template <class T> struct StencilDict {
   int32_t delta[kStencilSlots];
   T val[kStencilSlots];

@@ -1,7 +1,7 @@
 // operators: anything with mul!(y, A, x) (src/run.jl:21-22) -- stored sparse matrices in their device layouts, dense matrices, host / device callbacks
 // Part of the ONE translation unit of libkschur_hip.so: included by ks_hip.hip, in this order --
 //     ks_context.hpp -> ks_operators.hpp -> ks_workspace.hpp -> ks_backend.hpp -> (C ABI in ks_hip.hip)
-// -- and not meant to be included on its own (needs ks_context.hpp).
+// -- and not meant to be included on its own (needs ks_context.hpp and ks_csr_layout.hpp).
 #pragma once
 // ------------------------------------------------------------------------------------------------
 // operators
@@ -75,7 +75,7 @@ template <class D> struct CsrOp : ks_operator {
   uint8_t* codes = nullptr;
   int32_t* ddelta = nullptr;
   int dvi_unroll = 8;
-  int dvi_rpt = 4;          // rows per thread of k_spmv_dvi
+  int dvi_rpt = 1;          // rows per thread of k_spmv_dvi
   // halo plan (distributed)
   int64_t nghost = 0;
   D* ghost = nullptr;
@@ -668,527 +668,110 @@ inline void* upload_ptr(const std::vector<int64_t>& v, bool ptr64) {
   return d;
 }
 
+// device copy of the first `cnt` elements of v with `pad` more elements behind them; `zero`: the padding is zero-filled (a kernel
+// reads it), otherwise it is slack nothing interprets
+template <class T> T* upload_vec(const T* v, size_t cnt, size_t pad, bool zero = false) {
+  void* d = nullptr;
+  KS_HIP(hipMalloc(&d, (cnt + pad) * sizeof(T)));
+  if (zero) KS_HIP(hipMemset(d, 0, (cnt + pad) * sizeof(T)));
+  if (cnt) KS_HIP(hipMemcpy(d, v, cnt * sizeof(T), hipMemcpyHostToDevice));
+  return static_cast<T*>(d);
+}
+template <class T> T* upload_vec(const std::vector<T>& v, size_t pad, bool zero = false) { return upload_vec(v.data(), v.size(), pad, zero); }
+
+// the device arrays of a plan (ks_csr_layout.hpp) over the matrix (rp, ci, vv) it was made for
 template <class D>
-CsrOp<D>* make_csr(ks_ctx* ctx, int64_t nrows, int64_t nnz, const std::vector<int64_t>& rp,
-                   const std::vector<int32_t>& ci, const std::vector<D>& vv, int cb_mode = 0, int64_t nghost = 0, int64_t nlow = 0) {
-  // cb_mode: 0 = column blocks not allowed, 1 = allowed (decided below), 2 = this IS a column block (plain CSR row blocks,
-  //          nothing else is tried), 3 = allowed, row block of a distributed operator: columns >= nrows are ghost slots
-  //          (nghost of them, the first nlow owned by lower ranks -- they precede the local columns in the global order)
+CsrOp<D>* upload(ks_ctx* ctx, const CsrPlan<D>& P, int64_t nrows, int64_t nnz, const std::vector<int64_t>& rp, const std::vector<int32_t>& ci,
+                 const std::vector<D>& vv) {
   auto op = std::make_unique<CsrOp<D>>();
   op->ctx = ctx;
   op->n_local = nrows;
   op->nnz = nnz;
   op->dtype = sizeof(D) == 8 ? KS_F64 : KS_C64;
-  // int64-nnz CSR: offsets need 64 bits from 2^31 stored entries on (KS_SPMV_PTR64=1 forces it, for tests)
-  op->ptr64 = nnz >= (int64_t)2147483647 || env_int("KS_SPMV_PTR64", 0) != 0;
-  // Delta-value-indexed layout (k_spmv_dvi): at most 256 distinct (column - row, value) pairs -> one byte per
-  // non-zero.  KS_SPMV_FORMAT = csr | vi | dvi restricts the choice (default: the most compact that applies).
-  {
-    const char* fmt = cb_mode == 2 ? "csr" : std::getenv("KS_SPMV_FORMAT");
-    const bool try_dvi = nnz > 0 && (!fmt || std::string(fmt) == "dvi" || std::string(fmt) == "stencil");
-    if (try_dvi) {
-      struct Key {
-        uint64_t a, b;
-        int64_t d;
-        bool operator==(const Key& o) const { return a == o.a && b == o.b && d == o.d; }
-      };
-      struct KeyHash {
-        size_t operator()(const Key& k) const {
-          return std::hash<uint64_t>()((k.a * 0x9E3779B97F4A7C15ull ^ k.b) + (uint64_t)k.d * 0xC2B2AE3D27D4EB4Full);
-        }
-      };
-      std::unordered_map<Key, int, KeyHash> index;
-      std::vector<uint8_t> codes((size_t)nnz);
-      std::vector<int32_t> dd;
-      std::vector<D> dv;
-      bool ok = true;
-      int64_t max_row = 0;
-      Key ckey[8];
-      int cid[8], ncache = 0, cnext = 0;
-      std::vector<uint8_t> local_used(256, 0);   // dictionary entry used by at least one LOCAL column (ghost-only entries: the split product)
-      for (int64_t r = 0; r < nrows && ok; ++r) {
-        max_row = std::max(max_row, rp[r + 1] - rp[r]);
-        for (int64_t p = rp[r]; p < rp[r + 1]; ++p) {
-          Key k{0, 0, (int64_t)ci[p] - r};
-          std::memcpy(&k, &vv[p], sizeof(D));
-          // stencils cycle through a handful of keys: a tiny recent-key cache in front of the hash map
-          // (n = 1e8 rows / 7e8 non-zeros convert in seconds instead of half a minute)
-          bool hit = false;
-          for (int q = 0; q < ncache; ++q)
-            if (ckey[q] == k) { codes[p] = (uint8_t)cid[q]; hit = true; break; }
-          if (hit) { if (ci[p] < nrows) local_used[codes[p]] = 1; continue; }
-          auto it = index.find(k);
-          int id;
-          if (it == index.end()) {
-            if (dd.size() == 256) { ok = false; break; }
-            id = (int)dd.size();
-            index.emplace(k, id);
-            dd.push_back((int32_t)k.d);
-            dv.push_back(vv[p]);
-          } else {
-            id = it->second;
-          }
-          codes[p] = (uint8_t)id;
-          if (ci[p] < nrows) local_used[id] = 1;
-          ckey[cnext] = k;
-          cid[cnext] = id;
-          cnext = (cnext + 1) & 7;
-          if (ncache < 8) ++ncache;
-        }
+  op->layout = P.layout;
+  op->ptr64 = P.ptr64;
+  op->bytes_per_nnz = P.bytes_per_nnz;
+  op->aux_bytes = P.aux_bytes;
+  op->ndict = P.ndict;
+  constexpr size_t kPad16 = 16 / sizeof(D);  // 16 bytes of D
+  switch (P.layout) {
+    case KS_LAYOUT_STENCIL: {
+      op->nstencil = P.nstencil;
+      op->nstencil_local = P.nstencil_local;
+      op->stencil_mask_bytes = P.stencil_mask_bytes;
+      for (int k = 0; k < ksd::kStencilSlots; ++k) {
+        op->sdict.delta[k] = k < P.nstencil ? P.sdelta[k] : 0;
+        op->sdict.val[k] = k < P.nstencil ? P.sval[k] : D{};
       }
-      // Stencil-mask layout: <= 32 dictionary entries and every row a sub-sequence of ONE ordering of them (a
-      // topological order of "entry a precedes entry b in some row"): one bit per slot and row.  KS_SPMV_FORMAT=dvi
-      // keeps the byte-per-entry layout, =stencil insists on this one.
-      if (ok && dd.size() <= (size_t)ksd::kStencilSlots && !(fmt && std::string(fmt) == "dvi")) {
-        const int ns = (int)dd.size();
-        std::vector<uint32_t> succ((size_t)ns, 0u);  // succ[a] bit b: a directly precedes b in some row
-        for (int64_t r = 0; r < nrows; ++r)
-          for (int64_t p = rp[r] + 1; p < rp[r + 1]; ++p) succ[codes[p - 1]] |= 1u << codes[p];
-        // Kahn's algorithm on <= 32 nodes; ties broken by dictionary id (first appearance) -> deterministic
-        std::vector<int> indeg((size_t)ns, 0), order;
-        for (int a = 0; a < ns; ++a)
-          for (int b = 0; b < ns; ++b)
-            if (succ[a] >> b & 1u) indeg[b]++;
-        std::vector<char> done((size_t)ns, 0);
-        for (int it = 0; it < ns; ++it) {
-          int pick = -1;
-          for (int a = 0; a < ns; ++a)
-            if (!done[a] && indeg[a] == 0) { pick = a; break; }
-          if (pick < 0) break;  // a cycle: no common order
-          done[pick] = 1;
-          order.push_back(pick);
-          for (int b = 0; b < ns; ++b)
-            if (succ[pick] >> b & 1u) indeg[b]--;
-        }
-        bool sten = (int)order.size() == ns;
-        std::vector<int> slot((size_t)ns, 0);
-        for (int k = 0; k < (int)order.size(); ++k) slot[order[k]] = k;
-        const int mbytes = ns <= 8 ? 1 : 4;
-        std::vector<uint8_t> m8;
-        std::vector<uint32_t> m32;
-        if (sten) {
-          if (mbytes == 1) m8.assign((size_t)nrows, 0); else m32.assign((size_t)nrows, 0u);
-          for (int64_t r = 0; r < nrows && sten; ++r) {
-            uint32_t m = 0;
-            int last = -1;
-            for (int64_t p = rp[r]; p < rp[r + 1]; ++p) {
-              const int k = slot[codes[p]];
-              if (k <= last) { sten = false; break; }  // (a repeated entry in one row: not a sub-sequence)
-              last = k;
-              m |= 1u << k;
-            }
-            if (mbytes == 1) m8[r] = (uint8_t)m; else m32[r] = m;
-          }
-        }
-        if (sten) {
-          op->nstencil = ns;
-          // (trailing slots that only ever name ghost columns -- one stride per neighbour of a slab: rows using them are boundary rows)
-          op->nstencil_local = ns;
-          for (int k = ns - 1; k >= 0 && !local_used[order[k]]; --k) op->nstencil_local = k;
-          op->stencil_mask_bytes = mbytes;
-          for (int k = 0; k < ns; ++k) {
-            op->sdict.delta[k] = dd[order[k]];
-            op->sdict.val[k] = dv[order[k]];
-          }
-          for (int k = ns; k < ksd::kStencilSlots; ++k) { op->sdict.delta[k] = 0; op->sdict.val[k] = D{}; }
-          op->ndvi = 0;
-          op->layout = KS_LAYOUT_STENCIL;
-          op->bytes_per_nnz = (double)mbytes * (double)nrows / (double)nnz;
-          op->aux_bytes = 0.0;
-          const size_t mbytes_al = (size_t)round_up((int64_t)nrows + 2, 8) * mbytes;
-          KS_HIP(hipMalloc(&op->smask, mbytes_al));
-          KS_HIP(hipMemset(op->smask, 0, mbytes_al));
-          KS_HIP(hipMemcpy(op->smask, mbytes == 1 ? (const void*)m8.data() : (const void*)m32.data(), (size_t)nrows * mbytes, hipMemcpyHostToDevice));
-          op->smask2 = op->smask;
-          return op.release();
-        }
-        KS_REQUIRE(!(fmt && std::string(fmt) == "stencil"), KS_ERR_ARGUMENT, "KS_SPMV_FORMAT=stencil: the rows are not sub-sequences of one entry order");
-      }
-      if (ok) {
-        op->ndvi = (int)dd.size();
-        op->dvi_unroll = max_row <= 4 ? 4 : 8;
-        // rows per thread: 4 once there are enough 1024-row tiles to fill the device twice over, else fewer
-        // (KS_DVI_RPT overrides: 1, 2 or 4)
-        // rows per thread (KS_DVI_RPT = 1, 2 or 4).  Measured on the 216^3 Laplacian: 77.8 / 78.7 / 117 us for
-        // 1 / 2 / 4 -- the kernel is bound by instruction issue (byte decode, two dictionary reads and one gather per
-        // entry), not by memory latency, so more rows per thread only cost occupancy.
-        op->dvi_rpt = env_int("KS_DVI_RPT", 1);
-        op->bytes_per_nnz = 1.0;
-        op->layout = KS_LAYOUT_DVI;
-        op->aux_bytes = (op->ptr64 ? 8.0 : 4.0) * (double)(nrows + 1);
-        op->rowptr = upload_ptr(rp, op->ptr64);
-        KS_HIP(hipMalloc(&op->codes, (size_t)nnz + 64));
-        KS_HIP(hipMemset(op->codes, 0, (size_t)nnz + 64));
-        KS_HIP(hipMalloc(&op->ddelta, 256 * 4));
-        KS_HIP(hipMalloc(&op->val, 256 * sizeof(D)));
-        KS_HIP(hipMemcpy(op->codes, codes.data(), (size_t)nnz, hipMemcpyHostToDevice));
-        KS_HIP(hipMemcpy(op->ddelta, dd.data(), dd.size() * 4, hipMemcpyHostToDevice));
-        KS_HIP(hipMemcpy(op->val, dv.data(), dv.size() * sizeof(D), hipMemcpyHostToDevice));
-        return op.release();
-      }
+      // zeroed masks up to a multiple of 8 rows beyond nrows + 2: k_spmv_stencil2 and the marching kernels (ks_spmv_march.hpp) read
+      // the masks of two rows in one word (smask2)
+      const size_t pad = (size_t)(round_up(nrows + 2, 8) - nrows);
+      if (P.stencil_mask_bytes == 1) op->smask = upload_vec(P.mask8, pad, true);
+      else op->smask = upload_vec(P.mask32, pad, true);
+      op->smask2 = op->smask;
+      break;
     }
-  }
-  // Value-indexed layout (k_spmv_csr<.., VI>): at most 256 distinct stored values (compared bit for bit, so
-  // -0.0 and NaN payloads survive) and every column index below 2^24.  KS_SPMV_FORMAT=csr keeps plain CSR.
-  std::vector<D> dict;
-  std::vector<int32_t> packed;
-  {
-    const char* fmt = cb_mode == 2 ? "csr" : std::getenv("KS_SPMV_FORMAT");
-    bool try_vi = nnz > 0 && !(fmt && (std::string(fmt) == "csr" || std::string(fmt) == "dvi" || std::string(fmt) == "sell"));
-    if (try_vi) {
-      struct Key {
-        uint64_t a, b;
-        bool operator==(const Key& o) const { return a == o.a && b == o.b; }
-      };
-      struct KeyHash {
-        size_t operator()(const Key& k) const { return std::hash<uint64_t>()(k.a * 0x9E3779B97F4A7C15ull ^ k.b); }
-      };
-      std::unordered_map<Key, int, KeyHash> index;
-      Key last_key{0, 0};
-      int last_id = 0;
-      packed.resize((size_t)nnz);
-      for (int64_t p = 0; p < nnz && try_vi; ++p) {
-        Key k{0, 0};
-        std::memcpy(&k, &vv[p], sizeof(D));
-        int id;
-        if (p > 0 && k == last_key) {  // runs of equal values are the common case
-          if (ci[p] >= (1 << 24)) { try_vi = false; break; }
-          packed[p] = (int32_t)(((uint32_t)last_id << 24) | (uint32_t)ci[p]);
-          continue;
-        }
-        auto it = index.find(k);
-        if (it == index.end()) {
-          if (dict.size() == 256) { try_vi = false; break; }
-          id = (int)dict.size();
-          index.emplace(k, id);
-          dict.push_back(vv[p]);
-        } else {
-          id = it->second;
-        }
-        if (ci[p] >= (1 << 24)) { try_vi = false; break; }
-        packed[p] = (int32_t)(((uint32_t)id << 24) | (uint32_t)ci[p]);
-        last_key = k;
-        last_id = id;
+    case KS_LAYOUT_DVI:
+      op->ndvi = P.ndvi;
+      op->dvi_unroll = P.dvi_unroll;
+      op->dvi_rpt = P.dvi_rpt;
+      op->rowptr = upload_ptr(rp, P.ptr64);
+      op->codes = upload_vec(P.codes, 64, true);  // k_spmv_dvi stages the codes of a tile in 16-byte packs: 64 zero bytes behind them
+      op->ddelta = upload_vec(P.ddelta, 256 - P.ddelta.size());  // (the dictionaries are allocated at their full 256 entries)
+      op->val = upload_vec(P.dval, 256 - P.dval.size());
+      break;
+    case KS_LAYOUT_SELL:
+    case KS_LAYOUT_SELL_VI:
+      op->nslices = P.nslices;
+      op->sell_un = P.sell_un;
+      op->sell_entries = P.sell_entries;
+      op->sliceptr = upload_ptr(P.sliceptr, P.ptr64);
+      op->colidx = upload_vec(P.sell_col, 4);  // (16 bytes of slack behind indices and values; k_spmv_sell stays inside its slices)
+      if (P.ndict > 0) op->val = upload_vec(P.dict, 256 - P.dict.size());
+      else op->val = upload_vec(P.sell_val, kPad16);
+      if (!P.sell_perm.empty()) op->sperm = upload_vec(P.sell_perm, 0);
+      break;
+    case KS_LAYOUT_CSR_CB:
+      for (const CsrPlan<D>& cb : P.cblocks)
+        op->cblocks.emplace_back(upload<D>(ctx, cb, nrows, (int64_t)cb.sub_ci.size(), cb.sub_rp, cb.sub_ci, cb.sub_vv));
+      op->cb_from_ghost = P.cb_from_ghost;
+      op->cb_rpt = P.cb_rpt;
+      op->cb_ni = P.cb_ni;
+      break;
+    default: {  // KS_LAYOUT_CSR / KS_LAYOUT_CSR_VI: row blocks of k_spmv_csr
+      op->ni = P.ni;
+      op->row_gather = P.row_gather;
+      op->nlong = P.nlong;
+      op->nblk = P.nblk;
+      op->blkptr = upload_ptr(P.blkptr, P.ptr64);
+      op->blkrow = upload_vec(P.blkrow, P.blkrow.size() < 4 ? 4 - P.blkrow.size() : 0);  // (at least 16 bytes)
+      if (P.nlong > 0) {
+        op->blkpart = upload_vec(P.blkpart, 0);
+        KS_HIP(hipMalloc(&op->lpart, (size_t)P.lfirst.back() * sizeof(D)));
+        op->lrow = upload_vec(P.lrow, 0);
+        op->lfirst = upload_vec(P.lfirst, 0);
       }
-    }
-    if (!try_vi) { dict.clear(); packed.clear(); }
-  }
-  op->ndict = (int)dict.size();
-  // Storage order.  Sliced ELLPACK (k_spmv_sell, lane = row: coalesced index / value loads and, for banded matrices,
-  // coalesced gathers) when slicing the rows 64 at a time pads the matrix by at most 15 % -- uniform row lengths:
-  // stencils with variable coefficients, structured finite-element meshes, banded matrices; otherwise (ragged rows,
-  // where a lane per row would idle and the gathers are scattered anyway) the non-zero-parallel CSR blocks of k_spmv_csr.
-  // KS_SPMV_FORMAT=sell / sellvi force it (KS_SELL_SIGMA = window for sorting rows by length, multiple of 64, default:
-  // 1 = no permutation); csr / vi force the CSR blocks.
-  {
-    const char* fmt = cb_mode == 2 ? "csr" : std::getenv("KS_SPMV_FORMAT");
-    const std::string f = fmt ? fmt : "";
-    const bool force_sell = f == "sell" || f == "sellvi";
-    const bool allow_sell = force_sell || f.empty();
-    int sigma = std::max(1, env_int("KS_SELL_SIGMA", 1));
-    if (sigma > 1) sigma = (int)round_up(sigma, 64);
-    if (f == "sell") { dict.clear(); packed.clear(); op->ndict = 0; }
-    if (allow_sell && nrows > 0 && nnz > 0) {
-      // slice position -> row (identity unless sigma > 1: stable sort by descending length inside each window)
-      std::vector<int32_t> perm;
-      if (sigma > 1) {
-        perm.resize((size_t)nrows);
-        for (int64_t i = 0; i < nrows; ++i) perm[i] = (int32_t)i;
-        for (int64_t w0 = 0; w0 < nrows; w0 += sigma) {
-          const int64_t w1 = std::min<int64_t>(nrows, w0 + sigma);
-          std::stable_sort(perm.begin() + w0, perm.begin() + w1,
-                           [&](int32_t x_, int32_t y_) { return rp[x_ + 1] - rp[x_] > rp[y_ + 1] - rp[y_]; });
-        }
-      }
-      auto row_at = [&](int64_t pos) { return sigma > 1 ? (int64_t)perm[pos] : pos; };
-      const int64_t nsl = (nrows + 63) / 64;
-      std::vector<int64_t> sp((size_t)nsl + 1, 0);
-      int64_t wmax = 0;
-      for (int64_t sl = 0; sl < nsl; ++sl) {
-        int64_t w = 0;
-        for (int64_t pos = sl * 64; pos < std::min<int64_t>(nrows, sl * 64 + 64); ++pos) {
-          const int64_t r = row_at(pos);
-          w = std::max(w, rp[r + 1] - rp[r]);
-        }
-        wmax = std::max(wmax, w);
-        sp[sl + 1] = sp[sl] + 64 * w;
-      }
-      const int64_t padded = sp[nsl];
-      if (force_sell || (double)padded <= 1.15 * (double)nnz + 64.0) {
-        KS_REQUIRE(padded < ((int64_t)1 << 40), KS_ERR_ARGUMENT, "sliced-ELLPACK padding explodes: use KS_SPMV_FORMAT=csr");
-        if (padded >= (int64_t)2147483647) op->ptr64 = true;
-        const bool vi = op->ndict > 0;
-        std::vector<int32_t> sc((size_t)padded, -1);
-        std::vector<D> sv(vi ? 0 : (size_t)padded);
-        for (int64_t sl = 0; sl < nsl; ++sl)
-          for (int64_t pos = sl * 64; pos < std::min<int64_t>(nrows, sl * 64 + 64); ++pos) {
-            const int64_t r = row_at(pos);
-            const int64_t lane = pos - sl * 64;
-            for (int64_t p = rp[r], k = 0; p < rp[r + 1]; ++p, ++k) {
-              const int64_t q = sp[sl] + k * 64 + lane;
-              sc[q] = vi ? packed[p] : ci[p];
-              if (!vi) sv[q] = vv[p];
-            }
-          }
-        op->nslices = (int)nsl;
-        op->sell_un = wmax <= 4 ? 4 : 8;
-        op->sell_entries = padded;
-        op->layout = vi ? KS_LAYOUT_SELL_VI : KS_LAYOUT_SELL;
-        op->bytes_per_nnz = (vi ? 4.0 : 4.0 + sizeof(D)) * (double)padded / (double)nnz;
-        op->aux_bytes = (op->ptr64 ? 8.0 : 4.0) * (double)(nsl + 1) + (sigma > 1 ? 4.0 * (double)nrows : 0.0);
-        op->sliceptr = upload_ptr(sp, op->ptr64);
-        KS_HIP(hipMalloc(&op->colidx, (size_t)padded * 4 + 16));
-        KS_HIP(hipMemcpy(op->colidx, sc.data(), (size_t)padded * 4, hipMemcpyHostToDevice));
-        if (vi) {
-          KS_HIP(hipMalloc(&op->val, 256 * sizeof(D)));
-          KS_HIP(hipMemcpy(op->val, dict.data(), dict.size() * sizeof(D), hipMemcpyHostToDevice));
-        } else {
-          KS_HIP(hipMalloc(&op->val, (size_t)padded * sizeof(D) + 16));
-          KS_HIP(hipMemcpy(op->val, sv.data(), (size_t)padded * sizeof(D), hipMemcpyHostToDevice));
-        }
-        if (sigma > 1) {
-          KS_HIP(hipMalloc(&op->sperm, (size_t)nrows * 4));
-          KS_HIP(hipMemcpy(op->sperm, perm.data(), (size_t)nrows * 4, hipMemcpyHostToDevice));
-        }
-        return op.release();
-      }
-    }
-  }
-  // COLUMN BLOCKS (KS_LAYOUT_CSR_CB).  A matrix with scattered columns whose x is larger than one XCD's L2 (4 MiB) runs at
-  // the device's random-gather rate (config 3: 59 us at n = 1e6, 5.1x its algorithmic traffic through the fabric).  Split
-  // into column blocks -- block b holds the entries with column in [b n/NB, (b+1) n/NB) -- each launch gathers from an
-  // x block that stays L2 resident, and because the entries of a row are sorted by column the row sums are simply
-  // continued from launch to launch (k_spmv_csr's yacc): same additions in the same order, bit-identical y.  Measured
-  // (tools/colblock_probe.py, n = 1e6): 59.5 us whole, 2 blocks 23 + 23 us, 4 blocks 4 x 13 us (launch floor), 8: 8 x 9.
-  // Auto: plain CSR row blocks would be used, single GPU, x between 6 and 160 MiB, rows sorted by column and short, and
-  // at least half of the entries further than n/16 from the diagonal -> blocks of ~4 MiB of x, at most 8.
-  // KS_SPMV_COLBLOCKS = 0 off / k >= 2 force.
-  if ((cb_mode == 1 || cb_mode == 3) && op->ndict == 0 && nnz > 0) {
-    const int cb_env = env_int("KS_SPMV_COLBLOCKS", -1);  // (read per upload: tests switch it inside one process)
-    // Distributed operators (cb_mode 3): the referenced columns in GLOBAL order are [ghosts of lower ranks | local columns |
-    // ghosts of higher ranks]; key(c) is the position of local-extended column c in that order.  Blocks are ranges of keys
-    // that do not straddle a segment, so every block gathers either from x or from the ghost vector, and a row stored in
-    // global column order (what a row block of a sorted CSR matrix is) is summed in the same order as on one GPU.
-    const int64_t next = nrows + nghost;
-    auto key = [&](int64_t c) { return c < nrows ? nlow + c : (c - nrows < nlow ? c - nrows : c); };
-    const int64_t seg_lo[3] = {0, nlow, nlow + nrows}, seg_hi[3] = {nlow, nlow + nrows, next};
-    int nbk = 0;
-    if (cb_env != 0) {
-      bool sorted = true;
-      int64_t far = 0, maxrow = 0;
-      const int64_t fardist = std::max<int64_t>(1, next / 16);
-      for (int64_t r = 0; r < nrows && sorted; ++r) {
-        maxrow = std::max(maxrow, rp[r + 1] - rp[r]);
-        for (int64_t q = rp[r]; q < rp[r + 1]; ++q) {
-          if (q > rp[r] && key(ci[q]) < key(ci[q - 1])) { sorted = false; break; }
-          far += std::llabs(key(ci[q]) - (nlow + r)) > fardist;
-        }
-      }
-      const double xmb = (double)next * sizeof(D) / (1 << 20);
-      if (sorted && maxrow <= 4 * kBlock) {
-        if (cb_env >= 2) nbk = cb_env;
-        // block width ~ 4 MiB of x (measured optimum at n = 1e6: 2 blocks, 2e6: 4 blocks); beyond 8 blocks the y that is
-        // written and read back between the launches (16 n bytes each) eats the gain (n = 1e7: 8 blocks -11 %, 16: +35 %)
-        else if (xmb >= 6.0 && xmb <= 160.0 && 2 * far >= nnz) nbk = std::min(8, std::max(2, (int)std::lround(xmb / 4.0)));
-      }
-    }
-    if (nbk >= 2) {
-      nbk = std::min(nbk, ksd::kCbMaxBlocks);
-      // block boundaries in key space: nbk blocks shared out over the non-empty segments in proportion to their width
-      // (one segment -- a single GPU --: b n / nbk, as before)
-      std::vector<int64_t> bounds{0};
-      std::vector<int> bseg;
-      {
-        int nseg = 0;
-        for (int g = 0; g < 3; ++g) nseg += seg_hi[g] > seg_lo[g];
-        nbk = std::max(nbk, nseg);
-        int cnt[3] = {0, 0, 0}, used = 0;
-        for (int g = 0; g < 3; ++g)
-          if (seg_hi[g] > seg_lo[g]) { cnt[g] = std::max(1, (int)((double)nbk * (double)(seg_hi[g] - seg_lo[g]) / (double)next)); used += cnt[g]; }
-        while (used > std::min(nbk, ksd::kCbMaxBlocks)) {  // (rounding up the narrow segments): take from the segment with the most blocks
-          int g = 0;
-          for (int h = 1; h < 3; ++h) if (cnt[h] > cnt[g]) g = h;
-          if (cnt[g] <= 1) break;
-          --cnt[g]; --used;
-        }
-        while (used < nbk) {  // give the rest to the segment with the widest blocks
-          int g = -1;
-          for (int h = 0; h < 3; ++h)
-            if (cnt[h] > 0 && (g < 0 || (double)(seg_hi[h] - seg_lo[h]) / cnt[h] > (double)(seg_hi[g] - seg_lo[g]) / cnt[g])) g = h;
-          ++cnt[g]; ++used;
-        }
-        KS_REQUIRE(used <= ksd::kCbMaxBlocks, KS_ERR_INTERNAL, "column blocks: more segments than blocks");
-        for (int g = 0; g < 3; ++g)
-          for (int b = 0; b < cnt[g]; ++b) {
-            const int64_t w = seg_hi[g] - seg_lo[g];
-            bounds.push_back(b + 1 == cnt[g] ? seg_hi[g] : seg_lo[g] + (int64_t)(b + 1) * w / cnt[g]);
-            bseg.push_back(g);
-          }
-        nbk = used;
-      }
-      // single-launch form (k_spmv_csr_cb): largest segment (entries of a tile of 256 * RPT rows inside one column block)
-      // for every candidate RPT
-      constexpr int kRptCand[5] = {1, 2, 4, 8, 16};
-      int64_t maxseg[5] = {0, 0, 0, 0, 0};
-      bool small_ptrs = true;
-      for (int b = 0; b < nbk; ++b) {
-        const int64_t lo = bounds[b], hi = (b + 1 == nbk) ? (int64_t)1 << 40 : bounds[b + 1];
-        const bool from_ghost = bseg[b] != 1;
-        std::vector<int64_t> rpb((size_t)nrows + 1, 0);
-        std::vector<int32_t> cib;
-        std::vector<D> vvb;
-        for (int64_t r = 0; r < nrows; ++r) {
-          for (int64_t q = rp[r]; q < rp[r + 1]; ++q) {
-            const int64_t kq = key(ci[q]);
-            if (kq >= lo && kq < hi) { cib.push_back(from_ghost ? (int32_t)(ci[q] - nrows) : ci[q]); vvb.push_back(vv[q]); }
-          }
-          rpb[r + 1] = (int64_t)cib.size();
-        }
-        for (int k = 0; k < 5; ++k) {
-          const int64_t tr = (int64_t)kBlock * kRptCand[k];
-          for (int64_t r0 = 0; r0 < nrows; r0 += tr) maxseg[k] = std::max(maxseg[k], rpb[std::min(nrows, r0 + tr)] - rpb[r0]);
-        }
-        op->cblocks.emplace_back(make_csr<D>(ctx, nrows, (int64_t)cib.size(), rpb, cib, vvb, 2));
-        op->cb_from_ghost.push_back(from_ghost ? 1 : 0);
-        small_ptrs = small_ptrs && !op->cblocks.back()->ptr64;
-      }
-      // Measured (tools/cb_single_ab.py, profiles/r03_column_blocks.txt): the single launch wins where the y round trips of
-      // many blocks hurt (n = 1e7, 8 blocks: 858 -> 823 us) and loses a little where two to four launches were already close
-      // to what bounds this product -- the rate at which an XCD's L2 hands out randomly addressed lines, 5e6 of them for
-      // 1e6 rows: 46 us either way at n = 1e6, 100 vs 107 us at 2e6.  So: single launch from 5 blocks on
-      // (KS_SPMV_CB_SINGLE=0 never, KS_SPMV_CB_RPT=k forces it with k sub-tiles per workgroup).  A distributed operator
-      // always takes the single launch (the per-block launches have one x; the kernel takes a base per block).
-      const int rpt_force = env_int("KS_SPMV_CB_RPT", 0);
-      if (small_ptrs && (cb_mode == 3 || (env_int("KS_SPMV_CB_SINGLE", 1) && (nbk > 4 || rpt_force > 0)))) {
-        // all tiles resident at once (one round of workgroups keeps them in step on the same column block): the smallest RPT
-        // whose tile count fits, among those whose segments fit the LDS depth (8 x 256 products, 16 x 256 for Float64)
-        const int nimax = (int)(ksd::kSpmvCapBytes / (kBlock * sizeof(D)));  // 16 (Float64) / 8 (ComplexF64)
-        const int rpt_env = env_int("KS_SPMV_CB_RPT", 0);
-        int best = -1;
-        for (int k = 0; k < 5; ++k) {
-          const int ni = maxseg[k] <= 8 * kBlock ? 8 : (maxseg[k] <= 16 * kBlock && nimax >= 16 ? 16 : 0);
-          if (!ni) break;  // (segments only grow with RPT)
-          best = k;
-          const int64_t ntiles = (nrows + (int64_t)kBlock * kRptCand[k] - 1) / ((int64_t)kBlock * kRptCand[k]);
-          if (rpt_env ? kRptCand[k] >= rpt_env : ntiles <= (int64_t)ctx->num_cu * (ni == 8 ? 8 : 4)) break;
-        }
-        if (best >= 0) {
-          op->cb_rpt = kRptCand[best];
-          op->cb_ni = maxseg[best] <= 8 * kBlock ? 8 : 16;
-        }
-      }
-      if (cb_mode == 3 && !op->cb_rpt) {
-        // (no single-launch shape fits: row blocks of plain CSR below)
-        op->cblocks.clear();
-        op->cb_from_ghost.clear();
+      op->rowptr = upload_ptr(rp, P.ptr64);
+      // (two entries + 16 bytes of slack behind indices and values: k_spmv_csr and k_spmv_csr_cb guard every load by the block's
+      // entry count, nothing reads it)
+      if (P.ndict > 0) {
+        op->colidx = upload_vec(P.packed, 2 + 4);
+        op->val = upload_vec(P.dict, 256 - P.dict.size());
       } else {
-        op->layout = KS_LAYOUT_CSR_CB;
-        op->bytes_per_nnz = 4.0 + sizeof(D);
-        op->aux_bytes = 0.0;
-        for (auto& cbk : op->cblocks) op->aux_bytes += cbk->aux_bytes;
-        if (!op->cb_rpt) op->aux_bytes += (double)(nbk - 1) * 2.0 * sizeof(D) * (double)nrows;  // y written and read back between the blocks
-        return op.release();
+        op->colidx = upload_vec(ci.data(), (size_t)nnz, 2 + 4);
+        op->val = upload_vec(vv.data(), (size_t)nnz, 2 + kPad16);
       }
-    }
-  }
-  // Row blocks of k_spmv_csr.  A block holds at most ni * 256 products in LDS (<= 32 KiB; KS_SPMV_NI overrides), so
-  // regular matrices get full 256-row blocks and the LDS footprint (occupancy) follows the matrix.  Greedy pass over the
-  // rows: close the block at 256 rows or when the next row would overflow it; a row longer than the capacity becomes a
-  // block of its own (handled by all 256 threads).
-  {
-    const int nimax = (int)(ksd::kSpmvCapBytes / (kBlock * sizeof(D)));  // 16 (Float64) / 8 (ComplexF64)
-    // depth from the 90th percentile of the non-zeros of fixed 256-row tiles: a regular matrix gets exactly what its
-    // tiles need (7-point stencil: 1792 -> 7; 12 measured 14 % slower than 7 or 8 there: LDS footprint), the heavy tail
-    // of a skewed one gets shorter blocks instead of inflating everybody's LDS
-    std::vector<int64_t> tile_nnz;
-    for (int64_t r0 = 0; r0 < nrows; r0 += ksd::kSpmvRows) tile_nnz.push_back(rp[std::min<int64_t>(nrows, r0 + ksd::kSpmvRows)] - rp[r0]);
-    int64_t t90 = 0;
-    if (!tile_nnz.empty()) {
-      const size_t k = (tile_nnz.size() - 1) * 9 / 10;
-      std::nth_element(tile_nnz.begin(), tile_nnz.begin() + k, tile_nnz.end());
-      t90 = tile_nnz[k];
-    }
-    const int need = (int)((t90 + kBlock - 1) / kBlock);
-    int ni = need <= 4 ? 4 : need <= 7 ? 7 : need <= 8 ? 8 : need <= 12 ? 12 : 16;
-    ni = env_int("KS_SPMV_NI", ni);
-    if (ni != 4 && ni != 7 && ni != 8 && ni != 12 && ni != 16) ni = 16;
-    ni = std::min(ni, nimax);
-    op->ni = ni;
-    {
-      // ROW-GATHER or NON-ZERO-PARALLEL gathers (k_spmv_csr): with lane = row the gathers of one instruction are coalesced
-      // when neighbouring rows reference neighbouring columns (banded / stencil / FEM matrices: 212 -> 204 us on the 216^3
-      // Laplacian, 0.62 -> 0.64 of the HBM spec), and a chain of dependent LDS reads and scattered loads when they do not
-      // (hashed columns: 46.5 -> 49.5 us, heavy-tailed rows 109 -> 125 us).  Decided once from the matrix: the share of
-      // consecutive row pairs whose first stored columns are at most 16 apart.  KS_SPMV_CSR_ROWGATHER=0/1 forces.
-      int64_t pairs = 0, close = 0;
-      const int64_t stride = std::max<int64_t>(1, nrows / 65536);
-      for (int64_t r = 0; r + 1 < nrows; r += stride) {
-        if (rp[r + 1] == rp[r] || rp[r + 2] == rp[r + 1]) continue;
-        ++pairs;
-        const int64_t d = (int64_t)ci[rp[r + 1]] - (int64_t)ci[rp[r]];
-        if (d >= -16 && d <= 16) ++close;
-      }
-      const int rg_env = env_int("KS_SPMV_CSR_ROWGATHER", -1);
-      op->row_gather = rg_env >= 0 ? rg_env != 0 : (pairs > 0 && 2 * close >= pairs);
-    }
-    const int64_t cap = (int64_t)ni * kBlock;
-    std::vector<int64_t> bp{0};
-    std::vector<int32_t> br{0}, part, lrow, lfirst{0};
-    int64_t r = 0;
-    while (r < nrows) {
-      const int64_t first = rp[r + 1] - rp[r];
-      if (first > cap) {  // long row: chunk blocks of <= cap entries, all with row range [r, r+1)
-        for (int64_t q = rp[r]; q < rp[r + 1]; q += cap) {
-          part.push_back((int32_t)lfirst.back() + (int32_t)((q - rp[r]) / cap));
-          br.push_back((int32_t)(r + 1));
-          bp.push_back(std::min(q + cap, rp[r + 1]));
-          if (q + cap < rp[r + 1]) br.back() = (int32_t)r;  // the next chunk starts at the same row
-        }
-        lrow.push_back((int32_t)r);
-        lfirst.push_back(lfirst.back() + (int32_t)((first + cap - 1) / cap));
-        op->nlong++;
-        r += 1;
-        continue;
-      }
-      int64_t e = r + 1;
-      while (e < nrows && e - r < ksd::kSpmvRows && rp[e + 1] - rp[r] <= cap && rp[e + 1] - rp[e] <= cap) ++e;
-      part.push_back(-1);
-      br.push_back((int32_t)e);
-      bp.push_back(rp[e]);
-      r = e;
-    }
-    op->nblk = (int)br.size() - 1;
-    KS_REQUIRE((int64_t)br.size() - 1 < (int64_t)2147483647, KS_ERR_ARGUMENT, "too many row blocks");
-    op->blkptr = upload_ptr(bp, op->ptr64);
-    KS_HIP(hipMalloc(&op->blkrow, std::max<size_t>(br.size() * 4, 16)));
-    KS_HIP(hipMemcpy(op->blkrow, br.data(), br.size() * 4, hipMemcpyHostToDevice));
-    if (op->nlong > 0) {
-      KS_HIP(hipMalloc(&op->blkpart, part.size() * 4));
-      KS_HIP(hipMemcpy(op->blkpart, part.data(), part.size() * 4, hipMemcpyHostToDevice));
-      KS_HIP(hipMalloc(&op->lpart, (size_t)lfirst.back() * sizeof(D)));
-      KS_HIP(hipMalloc(&op->lrow, lrow.size() * 4));
-      KS_HIP(hipMemcpy(op->lrow, lrow.data(), lrow.size() * 4, hipMemcpyHostToDevice));
-      KS_HIP(hipMalloc(&op->lfirst, lfirst.size() * 4));
-      KS_HIP(hipMemcpy(op->lfirst, lfirst.data(), lfirst.size() * 4, hipMemcpyHostToDevice));
-    }
-  }
-  op->layout = op->ndict > 0 ? KS_LAYOUT_CSR_VI : KS_LAYOUT_CSR;
-  op->bytes_per_nnz = op->ndict > 0 ? 4.0 : 4.0 + sizeof(D);
-  op->aux_bytes = (op->ptr64 ? 8.0 : 4.0) * (double)(nrows + 1 + 2 * ((int64_t)op->nblk + 1));
-  op->rowptr = upload_ptr(rp, op->ptr64);
-  KS_HIP(hipMalloc(&op->colidx, (size_t)(nnz + 2) * 4 + 16));
-  if (op->ndict > 0) {
-    KS_HIP(hipMalloc(&op->val, 256 * sizeof(D)));
-    KS_HIP(hipMemcpy(op->colidx, packed.data(), (size_t)nnz * 4, hipMemcpyHostToDevice));
-    KS_HIP(hipMemcpy(op->val, dict.data(), dict.size() * sizeof(D), hipMemcpyHostToDevice));
-  } else {
-    KS_HIP(hipMalloc(&op->val, (size_t)(nnz + 2) * sizeof(D) + 16));
-    if (nnz) {
-      KS_HIP(hipMemcpy(op->colidx, ci.data(), (size_t)nnz * 4, hipMemcpyHostToDevice));
-      KS_HIP(hipMemcpy(op->val, vv.data(), (size_t)nnz * sizeof(D), hipMemcpyHostToDevice));
     }
   }
   return op.release();
+}
+
+// stored sparse matrix -> its device layout: planned on the host (ks_csr_layout.hpp), then uploaded
+template <class D>
+CsrOp<D>* make_csr(ks_ctx* ctx, int64_t nrows, int64_t nnz, const std::vector<int64_t>& rp, const std::vector<int32_t>& ci,
+                   const std::vector<D>& vv, CbMode cb_mode = CbMode::None, int64_t nghost = 0, int64_t nlow = 0) {
+  const CsrPlan<D> plan = plan_csr<D>(CsrHost<D>{nrows, nnz, rp, ci, vv}, FormatRequest::from_env(), cb_mode, nghost, nlow, ctx->num_cu);
+  return upload<D>(ctx, plan, nrows, nnz, rp, ci, vv);
 }
 
 }  // namespace

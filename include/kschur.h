@@ -480,6 +480,21 @@ int ks_host_schurfact(int dtype, void* H, int m, int n, int ldh, int start, int 
 int ks_host_restart_step(int dtype, void* H, int ldh, void* Q, int ldq, int maxdim, int mindim,
                          int nev, int which, double tol, int active, int* k, int* nlock, int* purge,
                          double* lams_c64, double* rs, int32_t* groups);
+/* Which device layout ks_operator_csr (nghost < 0: a whole matrix on one GPU) or ks_operator_csr_dist (nghost >= 0: a row
+ * block with local-extended columns, ncols = nrows_local + nghost, the first nlow ghost slots owned by lower ranks; nlow < 0:
+ * neighbours not in ascending order) would give this matrix under the current KS_SPMV_* environment, planned on the host:
+ * no device is touched.  `num_cu`: compute units of the device the plan is for (256 on an MI355X).  Out (each may be NULL):
+ * what ks_operator_format reports, aux_bytes (index structures streamed next to the non-zeros), facts[KS_PLAN_NFACTS]
+ * indexed by KS_PLAN_*, the stencil dictionary's column offsets in slot order (up to 32), the row blocks (nblk + 1 entries
+ * each, at most blk_cap) and the column-block boundaries in key space (blocks + 1 entries, at most cb_cap). */
+enum { KS_PLAN_PTR64 = 0, KS_PLAN_NI, KS_PLAN_NBLK, KS_PLAN_NLONG, KS_PLAN_ROW_GATHER, KS_PLAN_NSLICES, KS_PLAN_SELL_ENTRIES,
+       KS_PLAN_NCOLBLOCKS, KS_PLAN_CB_RPT, KS_PLAN_CB_NI, KS_PLAN_NSTENCIL, KS_PLAN_NSTENCIL_LOCAL, KS_PLAN_STENCIL_MASK_BYTES,
+       KS_PLAN_NDVI, KS_PLAN_DVI_UNROLL, KS_PLAN_NFACTS };
+int ks_host_csr_plan(int64_t nrows_local, int64_t ncols, int64_t nnz, const void* ptr, const void* idx,
+                     const void* val, int layout, int index_base, int index_type, int dtype, int num_cu,
+                     int64_t nghost, int64_t nlow, int* plan_layout, int* ndict, double* bytes_per_nnz,
+                     double* aux_bytes, int64_t* facts, int32_t* stencil_delta, int64_t* blkrow, int64_t* blkptr,
+                     int64_t blk_cap, int64_t* cb_bounds, int cb_cap);
 /* sortschur!(H, Q, nconv, ordering)   src/run.jl:465-502 */
 int ks_host_sortschur(int dtype, void* H, int m, int n, int ldh, void* Q, int nq, int ldq, int nconv,
                       int which);

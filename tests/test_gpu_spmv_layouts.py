@@ -8,40 +8,15 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+import layout_cases as lc
 from __graft_entry__ import import_package
+from layout_cases import rnd
 from oracle import arnoldi as oa
 from oracle.matrices import laplace3d
 
 pytestmark = pytest.mark.gpu
 pkg = import_package()
 DTYPES = [np.float64, np.complex128]
-
-
-def rnd(rng, dtype, *shape):
-    a = rng.standard_normal(shape)
-    if np.dtype(dtype).kind == "c":
-        a = a + 1j * rng.standard_normal(shape)
-    return a.astype(dtype)
-
-
-def _skewed(rng, dtype, n):
-    """Short random rows + empty rows + a band of 300-entry rows + rows far longer than any block capacity."""
-    cplx = np.dtype(dtype).kind == "c"
-    A = sp.random(n, n, density=4.0 / n, random_state=rng, format="lil", dtype=np.float64)
-    for r, cnt in ((3, 4097), (n // 3, 9000), (n - 2, 9000)):
-        c = rng.choice(n, cnt, replace=False)
-        A[r, c] = rng.standard_normal(cnt)
-    for r in range(n // 2, n // 2 + 40):
-        c = rng.choice(n, 300, replace=False)
-        A[r, c] = rng.standard_normal(300)
-    A[10:30, :] = 0
-    A = A.tocsr()
-    if cplx:
-        B = A.copy()
-        B.data = rng.standard_normal(B.nnz)
-        A = (A + 1j * B).tocsr()
-    A.sort_indices()
-    return A.astype(dtype)
 
 
 def _apply(A, x, dtype, ctx=None):
@@ -59,10 +34,8 @@ def test_csr_row_blocks_long_rows_and_64bit_offsets(dtype, ptr64, monkeypatch):
     (all-threads path), empty rows -- vs scipy to 1e-13 relative; the int64-offset instantiation (what a matrix with
     nnz >= 2^31 gets, forced by KS_SPMV_PTR64=1) must be BIT-identical to the int32 one; and the same matrix handed
     over as CSC / Int64 / 1-based (Julia's SparseMatrixCSC) builds the same operator."""
-    rng = np.random.default_rng(101)
-    n = 20011
-    A = _skewed(rng, dtype, n)
-    x = rnd(rng, dtype, n)
+    A, x = lc.skewed_case(dtype)
+    n = A.shape[0]
     monkeypatch.setenv("KS_SPMV_PTR64", ptr64)
     monkeypatch.setenv("KS_SPMV_FORMAT", "csr")
     y, fmt, op = _apply(A, x, dtype)
@@ -92,29 +65,14 @@ def test_sliced_ellpack_is_bit_identical_and_chosen_for_uniform_rows(dtype, monk
     """A 7-point stencil with VARIABLE coefficients (no dictionary layout applies) is stored as sliced ELLPACK by
     default; y must equal the CSR-block kernel's bit for bit.  Forced on a ragged matrix (heavy padding, empty rows,
     Inf in x next to padding) with and without sigma-window sorting it must still agree; a value-indexed SELL too."""
-    cplx = np.dtype(dtype).kind == "c"
-    rng = np.random.default_rng(55)
-    A = laplace3d(13, 14, 15).astype(dtype)
-    A.data = A.data * (1.0 + 0.5 * rng.random(A.nnz)) + (0.1j * rng.random(A.nnz) if cplx else 0)
-    n = A.shape[0]
-    x = rnd(rng, dtype, n)
+    A, x, R, xr = lc.varcoef_and_ragged(dtype)
     y, fmt, op = _apply(A, x, dtype)
     assert fmt["layout"] == "sell" and fmt["ndict"] == 0 and fmt["bytes_per_nnz"] < 1.15 * (4 + np.dtype(dtype).itemsize)
     monkeypatch.setenv("KS_SPMV_FORMAT", "csr")
     y_csr, f_csr, _ = _apply(A, x, dtype, op.ctx)
     assert f_csr["layout"] == "csr" and np.array_equal(y.view(np.uint64), y_csr.view(np.uint64))
     np.testing.assert_allclose(y, A @ x, rtol=1e-13, atol=1e-13)
-    # ragged: rows of 0..40 entries, a few distinct values
-    m = 5003
-    R = sp.random(m, m, density=8.0 / m, random_state=rng, format="csr", dtype=np.float64)
-    R.data = np.array([1.5, -2.0, 0.25, -0.0])[rng.integers(0, 4, R.nnz)]
-    R = R.tolil()
-    R[100:164, :] = 0
-    R[7, rng.choice(m, 40, replace=False)] = 3.0
-    R = R.tocsr().astype(dtype)
-    R.sort_indices()
-    xr = rnd(rng, dtype, m)
-    xr[rng.choice(m, 5, replace=False)] = np.inf  # a padding entry must never be multiplied
+    # ragged: rows of 0..40 entries, a few distinct values; Inf in xr (a padding entry must never be multiplied)
     ref, _, op2 = _apply(R, xr, dtype)
     assert _["layout"] == "csr"
     for fmt_name, sigma in (("sell", "1"), ("sell", "256"), ("sellvi", "1"), ("sellvi", "640")):
@@ -176,24 +134,9 @@ def test_stencil_mask_layout(dtype, monkeypatch):
     using the same two dictionary entries in opposite orders) falls back to the delta-value-indexed layout;
     KS_SPMV_FORMAT=stencil then refuses.  (iv) 33 dictionary entries: too many slots -> DVI."""
     cplx = np.dtype(dtype).kind == "c"
-    rng = np.random.default_rng(91)
-    mx, my, mz = 9, 8, 7
-    n = mx * my * mz
-    rows, cols, vals = [], [], []
-    offs = [(dx, dy, dz) for dz in (-1, 0, 1) for dy in (-1, 0, 1) for dx in (-1, 0, 1) if abs(dx) + abs(dy) + abs(dz) <= 2]
-    coef = {o: (rng.standard_normal() + (1j * rng.standard_normal() if cplx else 0)) for o in offs}
-    for z in range(mz):
-        for y in range(my):
-            for x_ in range(mx):
-                r = x_ + mx * (y + my * z)
-                for (dx, dy, dz) in offs:
-                    if 0 <= x_ + dx < mx and 0 <= y + dy < my and 0 <= z + dz < mz:
-                        rows.append(r); cols.append(r + dx + mx * (dy + my * dz)); vals.append(coef[(dx, dy, dz)])
-    A = sp.csr_matrix((np.array(vals, dtype=dtype), (rows, cols)), shape=(n, n))
-    A.sort_indices()
-    xv = rnd(rng, dtype, n)
+    A, xv, rng = lc.stencil19(dtype)
     y, f, op = _apply(A, xv, dtype)
-    assert f["layout"] == "stencil" and f["ndict"] == len(offs) == 19
+    assert f["layout"] == "stencil" and f["ndict"] == 19
     monkeypatch.setenv("KS_SPMV_FORMAT", "csr")
     y0, f0, _ = _apply(A, xv, dtype, op.ctx)
     assert f0["layout"] == "csr" and np.array_equal(y.view(np.uint64), y0.view(np.uint64))
@@ -209,25 +152,9 @@ def test_stencil_mask_layout(dtype, monkeypatch):
     fin = np.isfinite(ref)
     assert np.array_equal(np.isfinite(yi), fin) and np.allclose(yi[fin], ref[fin], rtol=1e-13, atol=1e-13)
     # (iii)
-    B = sp.csr_matrix(np.array([[0, 2.0, 0, 3.0], [0, 0, 0, 0], [0, 0, 0, 0], [0, 0, 0, 0.0]]))  # row 0: deltas (+1: 2.0), (+3: 3.0)
-    B = sp.lil_matrix((6, 6))
-    B[0, 1], B[0, 3] = 2.0, 3.0        # entries (delta 1, 2.0) then (delta 3, 3.0)
-    B[2, 3], B[2, 5] = 3.0, 2.0        # entries (delta 1, 3.0) then (delta 3, 2.0): fine so far (4 distinct entries)
-    B[3, 4], B[3, 5] = 2.0, 9.0        # (delta 1, 2.0) then (delta 2, 9.0)
-    B[1, 3], B[1, 4] = 9.0, 3.0        # (delta 2, 9.0) then (delta 3, 3.0)  -> 2.0@1 < 9.0@2 < 3.0@3 consistent
-    C2 = sp.lil_matrix((6, 6))
-    C2[0, 1], C2[0, 2] = 5.0, 7.0      # (delta 1, 5.0) precedes (delta 2, 7.0)
-    C2[3, 5] = 7.0                      # (delta 2, 7.0) alone
-    C2[2, 4], C2[2, 3] = 7.0, 5.0      # row 2: (delta 1, 5.0) then (delta 2, 7.0) again -- consistent; make a cycle instead:
-    D = sp.csr_matrix((np.array([5.0, 7.0, 7.0, 5.0]), (np.array([0, 0, 2, 2]), np.array([1, 2, 3, 5]))), shape=(6, 6))
-    # row 0: (delta 1, 5.0), (delta 2, 7.0);  row 2: (delta 1, 7.0), (delta 3, 5.0) -> four distinct entries, still acyclic
-    E = sp.csr_matrix((np.array([5.0, 7.0, 7.0, 5.0]), (np.array([0, 0, 3, 3]), np.array([1, 2, 4, 5]))), shape=(6, 6))
-    # row 0: (d1, 5), (d2, 7);  row 3: (d1, 7), (d2, 5): distinct entries (d1,5) (d2,7) (d1,7) (d2,5): acyclic as well.
-    # A genuine conflict needs the SAME two entries in both orders, which sorted columns forbid (same deltas, same order);
-    # unsorted CSR input can do it:
-    ptr = np.array([0, 2, 2, 4, 4, 4, 4], dtype=np.int64)
-    idx = np.array([1, 2, 4, 3], dtype=np.int64)            # row 0: cols 1, 2;  row 2: cols 4, 3 (unsorted)
-    val = np.array([5.0, 7.0, 7.0, 5.0]).astype(dtype)       # row 0: (d1,5),(d2,7); row 2: (d2,7),(d1,5)  -> cycle
+    # A conflict needs the SAME two entries in both orders, which sorted columns forbid (same deltas, same order); unsorted CSR
+    # input can do it: row 0: (d1,5),(d2,7); row 2: (d2,7),(d1,5)  -> cycle
+    ptr, idx, val = lc.opposite_orders(dtype)
     import ctypes as C
 
     Lh = pkg._lib.load()
@@ -250,9 +177,8 @@ def test_stencil_mask_layout(dtype, monkeypatch):
     assert rc == pkg._lib.KS_ERR_ARGUMENT
     monkeypatch.delenv("KS_SPMV_FORMAT")
     # (iv) a banded matrix with 33 distinct diagonals
-    n4 = 400
-    diags = [np.full(n4 - k, 1.0 + k) for k in range(33)]
-    G = sp.diags(diags, list(range(33)), format="csr").astype(dtype)
+    G = lc.banded33(dtype)
+    n4 = G.shape[0]
     y4, f4, _ = _apply(G, rnd(rng, dtype, n4), dtype, op.ctx)
     assert f4["layout"] == "csr-dvi" and f4["ndict"] == 33
 
@@ -282,23 +208,7 @@ def test_column_blocked_csr_is_bit_identical(dtype, monkeypatch):
     in CSR order -- y must equal the plain CSR row-block layout BIT for bit, for 2, 3 and 5 blocks, with empty rows, rows
     confined to one block and rows that span all of them; the auto rule picks it for config 3's matrix (n = 1e6: x = 8 MB,
     scattered columns) and leaves a banded matrix alone."""
-    rng = np.random.default_rng(11)
-    n = 30_000
-    A = sp.random(n, n, density=6.0 / n, random_state=rng, format="lil", dtype=np.float64)
-    A[100:140, :] = 0                                   # empty rows
-    for r in range(200, 260):                           # rows confined to the first / last column block
-        A[r, :] = 0
-        A[r, rng.choice(n // 8, 5, replace=False)] = rng.standard_normal(5)
-        A[r + 100, :] = 0
-        A[r + 100, n - 1 - rng.choice(n // 8, 5, replace=False)] = rng.standard_normal(5)
-    A = A.tocsr()
-    if np.dtype(dtype).kind == "c":
-        B = A.copy()
-        B.data = rng.standard_normal(B.nnz)
-        A = (A + 1j * B).tocsr()
-    A = A.astype(dtype)
-    A.sort_indices()
-    x = rnd(rng, dtype, n)
+    A, x, rng = lc.colblock_matrix(dtype)
     monkeypatch.setenv("KS_SPMV_FORMAT", "csr")
     monkeypatch.setenv("KS_SPMV_COLBLOCKS", "0")
     y0, f0, _ = _apply(A, x, dtype)
@@ -323,27 +233,20 @@ def test_column_blocked_csr_is_bit_identical(dtype, monkeypatch):
         monkeypatch.delenv("KS_SPMV_CB_SINGLE")
     # unsorted rows: the order of the additions would change -> the layout must refuse
     monkeypatch.setenv("KS_SPMV_COLBLOCKS", "2")
-    U = A.copy()
-    U.has_sorted_indices = False
-    r = 5000
-    a, b = U.indptr[r], U.indptr[r + 1]
-    if b - a >= 2:
-        U.indices[a:b] = U.indices[a:b][::-1].copy()
-        U.data[a:b] = U.data[a:b][::-1].copy()
-        yu, fu, _ = _apply(U, x, dtype)
-        assert fu["layout"] == "csr"
+    U = lc.reversed_row(A, 5000)
+    assert U is not None
+    yu, fu, _ = _apply(U, x, dtype)
+    assert fu["layout"] == "csr"
     monkeypatch.delenv("KS_SPMV_FORMAT")
     monkeypatch.delenv("KS_SPMV_COLBLOCKS")
     if np.dtype(dtype).kind == "f":
-        H = pkg.matrices.hashed_nonsymmetric_csr(1_000_000, seed=7)
-        xh = rnd(rng, dtype, H.shape[0])
+        H, xh, Bd = lc.colblock_big(rng, pkg, dtype)
         yh, fh, _ = _apply(H, xh, dtype)
         assert fh["layout"] == "csr-cb", fh
         monkeypatch.setenv("KS_SPMV_COLBLOCKS", "0")
         yp, fp, _ = _apply(H, xh, dtype)
         assert fp["layout"] == "csr" and np.array_equal(yh, yp)
         monkeypatch.delenv("KS_SPMV_COLBLOCKS")
-        Bd = sp.diags([rng.standard_normal(1_000_000 - abs(k)) for k in (-3, -1, 0, 1, 3)], [-3, -1, 0, 1, 3], format="csr")
         _, fb, _ = _apply(Bd, xh, dtype)
         assert fb["layout"] != "csr-cb", fb
 
