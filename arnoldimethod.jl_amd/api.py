@@ -327,6 +327,59 @@ def splu_operator(lu, ctx: Context | None = None) -> Operator:
     return lu_operator(lu.L, lu.U, perm_in=inv_r, perm_out=inv_c, ctx=ctx)
 
 
+def _tridiag_args(dl, d, du, sigma):
+    cplx = any(np.asarray(a).dtype.kind == "c" for a in (dl, d, du)) or isinstance(sigma, (complex, np.complexfloating))
+    dt = np.dtype(np.complex128 if cplx else np.float64)
+    arrs = [np.ascontiguousarray(a, dtype=dt) for a in (dl, d, du)]
+    n = arrs[1].shape[0] if arrs[1].ndim == 1 else -1
+    if n < 0 or arrs[0].shape != (max(n - 1, 0),) or arrs[2].shape != (max(n - 1, 0),):
+        raise DimensionMismatch(f"d must be a vector of n entries, dl and du of n - 1: {[a.shape for a in arrs]}")
+    sg = complex(sigma)
+    return dt, n, arrs, sg.real, sg.imag
+
+
+def tridiagonal_solve_operator(dl, d, du, sigma=0.0, ctx: Context | None = None, block_rows: int = 0) -> Operator:
+    """y = (T - sigma I)^-1 x for the tridiagonal T with sub-/main/super-diagonals dl (n-1), d (n), du (n-1): the
+    `ldiv!(y, F, x)` of the reference's shift-invert recipe (docs/src/index.md:234-259) on a 1-D operator, as a LIBRARY
+    operator (`ks_operator_tridiag_solve`): factored once on the host at upload (recursive separator elimination, pivoted LU
+    per block of `block_rows` rows, 0 = 64), applied by the library's own kernels with every vector resident in HBM.  The
+    eigenvalues of T closest to sigma are sigma + 1/theta for the largest-magnitude theta.  `operator.tridiag_info`: levels,
+    rows per level, blocks the planner shortened, largest block growth, backward error of the check solve."""
+    ctx = ctx or default_context()
+    lib = _lib.load()
+    dt, n, arrs, sre, sim = _tridiag_args(dl, d, du, sigma)
+    ptr = lambda a: None if a.size == 0 else a.ctypes.data  # noqa: E731
+    h = C.c_void_p()
+    check(lib.ks_operator_tridiag_solve(ctx._h, n, _dtype_code(dt), ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), sre, sim, int(block_rows), C.byref(h)))
+    op = Operator(ctx, h, (n, n), dt)
+    lv, sh, gr, res = C.c_int(), C.c_int64(), C.c_double(), C.c_double()
+    rows = np.zeros(8, dtype=np.int64)
+    check(lib.ks_operator_tridiag_info(h, C.byref(lv), rows.ctypes.data, C.byref(sh), C.byref(gr), C.byref(res)))
+    op.tridiag_info = dict(levels=lv.value, level_rows=[int(r) for r in rows[: lv.value]], shortened_blocks=sh.value, max_growth=gr.value,
+                           residual=res.value)
+    return op
+
+
+def host_tridiagonal_solve(dl, d, du, b, sigma=0.0, block_rows: int = 0):
+    """The host path of `tridiagonal_solve_operator` (`ks_host_tridiag_solve` / `ks_host_tridiag_info`, no device): plan, factors
+    and the apply that walks the arrays the device kernels read.  `b`: (n,) or (n, nrhs).  Returns (x, info) with info as
+    `operator.tridiag_info`."""
+    lib = _lib.load()
+    dt, n, arrs, sre, sim = _tridiag_args(dl, d, du, sigma)
+    B = np.asarray(b, dtype=dt)
+    cols = np.asfortranarray(B.reshape(n, -1))
+    X = np.zeros_like(cols, order="F")
+    ptr = lambda a: None if a.size == 0 else a.ctypes.data  # noqa: E731
+    lv, sh, gr, res = C.c_int(), C.c_int64(), C.c_double(), C.c_double()
+    rows = np.zeros(8, dtype=np.int64)
+    check(lib.ks_host_tridiag_solve(n, _dtype_code(dt), ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), sre, sim, int(block_rows), cols.shape[1],
+                                    ptr(cols), max(n, 1), ptr(X), max(n, 1), C.byref(lv), C.byref(gr), C.byref(res)))
+    check(lib.ks_host_tridiag_info(n, _dtype_code(dt), ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), sre, sim, int(block_rows), C.byref(lv),
+                                   rows.ctypes.data, C.byref(sh), C.byref(gr), C.byref(res)))
+    info = dict(levels=lv.value, level_rows=[int(r) for r in rows[: lv.value]], shortened_blocks=sh.value, max_growth=gr.value, residual=res.value)
+    return X.reshape(B.shape), info
+
+
 def host_operator(fn, n: int, dtype=np.float64, ctx: Context | None = None) -> Operator:
     """Opaque host operator: `fn(y, x)` fills y = A*x on numpy views (a LinearMap wrapping ldiv!,
     docs/src/index.md:246-249).  Columns are staged over PCIe by the library."""

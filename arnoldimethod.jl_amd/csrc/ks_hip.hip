@@ -39,6 +39,7 @@ using ksd::kBlock;
 #include "ks_csr_layout.hpp" // host-only: which layout a stored matrix gets, and its host arrays
 #include "ks_operators.hpp"  // ks_operator and its layouts
 #include "ks_sptrsv.hpp"     // shift-invert operator from triangular factors (sparse triangular solves)
+#include "ks_tridiag.hpp"    // tridiagonal shift-invert operator: factored once on the host (ks_tridiag_plan.hpp), applied in HBM
 #include "ks_workspace.hpp"  // ks_workspace, launch helpers, expansion, rotations
 #include "ks_block.hpp"      // s-step (block) expansion: launchers, shifts, block sizes
 #include "ks_backend.hpp"    // HipBackend, residual checks, placement search
@@ -467,6 +468,36 @@ int ks_operator_lu_layout(const ks_operator* op, int upper, int64_t* rows, int64
     if (auto* a = dynamic_cast<const LuOp<double>*>(op)) fill(a);
     else if (auto* b = dynamic_cast<const LuOp<cd>*>(op)) fill(b);
     else throw KsError{KS_ERR_ARGUMENT, "ks_operator_lu_layout: not an operator made by ks_operator_lu"};
+  });
+}
+
+int ks_operator_tridiag_solve(ks_ctx* ctx, int64_t n, int dtype, const void* dl, const void* d, const void* du, double sigma_re,
+                              double sigma_im, int block_rows, ks_operator** out) {
+  return guarded([&] {
+    KS_REQUIRE(ctx && out, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
+    KS_REQUIRE(dtype == KS_C64 || sigma_im == 0.0, KS_ERR_ARGUMENT, "ks_operator_tridiag_solve: a complex shift needs KS_C64 diagonals");
+    KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, "ks_operator_tridiag_solve: single-GPU contexts only (the elimination does not shard by rows)");
+    ctx->use();
+    *out = dtype == KS_F64 ? make_tridiag<double>(ctx, n, dl, d, du, sigma_re, sigma_im, block_rows)
+                           : make_tridiag<cd>(ctx, n, dl, d, du, sigma_re, sigma_im, block_rows);
+  });
+}
+
+int ks_operator_tridiag_info(const ks_operator* op, int* levels, int64_t* level_rows, int64_t* shortened_blocks, double* max_growth,
+                             double* residual) {
+  return guarded([&] {
+    KS_REQUIRE(op, KS_ERR_ARGUMENT, "null operator");
+    auto fill = [&](auto* t) {
+      if (levels) *levels = (int)t->level_rows.size();
+      for (int l = 0; level_rows && l < td::kMaxLevels; ++l) level_rows[l] = l < (int)t->level_rows.size() ? t->level_rows[l] : 0;
+      if (shortened_blocks) *shortened_blocks = t->shortened;
+      if (max_growth) *max_growth = t->max_growth;
+      if (residual) *residual = t->residual;
+    };
+    if (auto* a = dynamic_cast<const TridiagSolveOp<double>*>(op)) fill(a);
+    else if (auto* b = dynamic_cast<const TridiagSolveOp<cd>*>(op)) fill(b);
+    else throw KsError{KS_ERR_ARGUMENT, "ks_operator_tridiag_info: not an operator made by ks_operator_tridiag_solve"};
   });
 }
 
@@ -1412,6 +1443,29 @@ int ks_host_csr_plan(int64_t nrows_local, int64_t ncols, int64_t nnz, const void
       }
       for (int b = 0; cb_bounds && b < (int)P.cb_bounds.size() && b < cb_cap; ++b) cb_bounds[b] = P.cb_bounds[b];
     });
+  });
+}
+
+int ks_host_tridiag_solve(int64_t n, int dtype, const void* dl, const void* d, const void* du, double sigma_re, double sigma_im,
+                          int block_rows, int nrhs, const void* b, int64_t ldb, void* x, int64_t ldx, int* levels, double* max_growth,
+                          double* residual) {
+  return guarded([&] {
+    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
+    KS_REQUIRE(dtype == KS_C64 || sigma_im == 0.0, KS_ERR_ARGUMENT, "ks_host_tridiag_solve: a complex shift needs KS_C64 diagonals");
+    KS_REQUIRE(nrhs >= 0 && (nrhs == 0 || (b && x && b != x && ldb >= n && ldx >= n)), KS_ERR_ARGUMENT,
+               "ks_host_tridiag_solve: right-hand sides need distinct b and x with ldb, ldx >= n");
+    if (dtype == KS_F64) td::host_solve<double>(n, dl, d, du, sigma_re, sigma_im, block_rows, nrhs, b, ldb, x, ldx, levels, nullptr, nullptr, max_growth, residual);
+    else td::host_solve<cplx>(n, dl, d, du, sigma_re, sigma_im, block_rows, nrhs, b, ldb, x, ldx, levels, nullptr, nullptr, max_growth, residual);
+  });
+}
+
+int ks_host_tridiag_info(int64_t n, int dtype, const void* dl, const void* d, const void* du, double sigma_re, double sigma_im,
+                         int block_rows, int* levels, int64_t* level_rows, int64_t* shortened_blocks, double* max_growth, double* residual) {
+  return guarded([&] {
+    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
+    KS_REQUIRE(dtype == KS_C64 || sigma_im == 0.0, KS_ERR_ARGUMENT, "ks_host_tridiag_info: a complex shift needs KS_C64 diagonals");
+    if (dtype == KS_F64) td::host_solve<double>(n, dl, d, du, sigma_re, sigma_im, block_rows, 0, nullptr, 0, nullptr, 0, levels, level_rows, shortened_blocks, max_growth, residual);
+    else td::host_solve<cplx>(n, dl, d, du, sigma_re, sigma_im, block_rows, 0, nullptr, 0, nullptr, 0, levels, level_rows, shortened_blocks, max_growth, residual);
   });
 }
 

@@ -11,6 +11,9 @@ vector resident in HBM instead of crossing PCIe twice per product.
                                                the host (scipy), both triangular solves of every product on the device
                                                through the LIBRARY's own operator `ks_operator_lu` (hand-written
                                                synchronisation-free solve, csrc/ks_sptrsv.hpp) -- no vendor call, no torch.
+
+The LIBRARY's own tridiagonal shift-invert -- factored once at upload, applied by its own kernels, no rocSPARSE and no torch --
+is `api.tridiagonal_solve_operator(dl, d, du, sigma)` (`ks_operator_tridiag_solve`, csrc/ks_tridiag.hpp).
 """
 from __future__ import annotations
 

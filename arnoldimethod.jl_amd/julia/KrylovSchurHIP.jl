@@ -46,7 +46,7 @@ using LinearAlgebra, SparseArrays, Random
 import ArnoldiMethod
 import ArnoldiMethod: ArnoldiWorkspace, PartialSchur
 
-export HipContext, HipOperator, HipWorkspace, HipBasis, HipColumn, HipColumns, hip_partialschur, hip_partialschur!, hip_partialeigen, set_sstep!, relation_breaks
+export HipContext, HipOperator, HipTridiagonalSolve, tridiag_info, HipWorkspace, HipBasis, HipColumn, HipColumns, hip_partialschur, hip_partialschur!, hip_partialeigen, set_sstep!, relation_breaks
 
 const LIB = get(ENV, "KSCHUR_LIB", joinpath(@__DIR__, "..", "libkschur_hip.so"))
 
@@ -193,6 +193,35 @@ function lu_info(A::HipOperator)
     v = [Ref{Int64}(0) for _ in 1:4]
     check(ccall((:ks_operator_lu_info, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}), A.h, v[1], v[2], v[3], v[4]))
     (nnz_l = v[1][], nnz_u = v[2][], levels_l = v[3][], levels_u = v[4][])
+end
+
+# Shift-invert on a TRIDIAGONAL matrix (the recipe of docs/src/index.md:234-259 on a 1-D operator): mul!(y, A, x) with
+# A = (T - sigma*I)^-1.  The library factors T - sigma*I once on the host at upload (recursive separator elimination, pivoted
+# LU per block) and applies it with its own kernels, every vector resident in HBM (ks_operator_tridiag_solve): no host ldiv!,
+# no vendor solver.  `dl`, `du`: sub- / super-diagonal (n - 1 entries), `d`: diagonal; a `Tridiagonal` goes over as it is.
+function HipTridiagonalSolve(ctx::HipContext, dl::AbstractVector, d::AbstractVector, du::AbstractVector; sigma::Number = 0.0, block_rows::Integer = 0)
+    T = (eltype(dl) <: Complex || eltype(d) <: Complex || eltype(du) <: Complex || sigma isa Complex) ? ComplexF64 : Float64
+    n = length(d)
+    (length(dl) == n - 1 && length(du) == n - 1) || throw(DimensionMismatch("dl and du must have $(n - 1) entries"))
+    a = Vector{T}(dl); b = Vector{T}(d); c = Vector{T}(du)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve a b c begin
+        check(ccall((:ks_operator_tridiag_solve, LIB), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Cint, Ref{Ptr{Cvoid}}),
+                    ctx.h, n, dtype_code(T), pointer(a), pointer(b), pointer(c), Float64(real(sigma)), Float64(imag(sigma)), Cint(block_rows), r))
+    end
+    _finish_operator(T, r[], n, ctx, nothing)
+end
+HipTridiagonalSolve(ctx::HipContext, A::Tridiagonal; kw...) = HipTridiagonalSolve(ctx, A.dl, A.d, A.du; kw...)
+
+"What the planner of a tridiagonal shift-invert operator made of the matrix: levels, rows per level, shortened blocks, growth, check residual."
+function tridiag_info(A::HipOperator)
+    lv = Ref{Cint}(0); rows = zeros(Int64, 8); sh = Ref{Int64}(0); gr = Ref{Cdouble}(0); res = Ref{Cdouble}(0)
+    GC.@preserve rows begin
+        check(ccall((:ks_operator_tridiag_info, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}, Ptr{Int64}, Ref{Int64}, Ref{Cdouble}, Ref{Cdouble}),
+                    A.h, lv, pointer(rows), sh, gr, res))
+    end
+    (levels = Int(lv[]), level_rows = rows[1:lv[]], shortened_blocks = sh[], max_growth = gr[], residual = res[])
 end
 
 "Device layout the library chose for a stored matrix: (bytes streamed per non-zero, dictionary size, layout code)."

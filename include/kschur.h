@@ -169,6 +169,26 @@ int ks_operator_lu_info(const ks_operator* op, int64_t* nnz_l, int64_t* nnz_u, i
  * of an inverted dense run), rows in such runs, rows of the part next to the root of the elimination tree that runs on one
  * XCD, and the number of independent groups the rest was split into (0: one launch for everything) */
 int ks_operator_lu_layout(const ks_operator* op, int upper, int64_t* rows, int64_t* run_rows, int64_t* top_rows, int* ngroups);
+/* (v) tridiagonal shift-invert, factored once:  y = (T - sigma I)^-1 x  for tridiagonal T -- the `ldiv!(y, F, x)` of the
+ * LinearMap the reference's shift-invert recipe wraps around F = factorize(A - sigma I)  (docs/src/index.md:234-259), for a 1-D
+ * operator.  Recursive separator elimination: the rows are split into blocks of at most `block_rows` rows with one separator row
+ * between neighbours; per block a partially pivoted LU and its two spikes are computed ON THE HOST at upload, the separators'
+ * Schur system (tridiagonal again) becomes the next level, and a level of at most 2 block_rows rows is solved outright.  A
+ * product is one launch per level down, one per level back up (5 at n = 5e5), every vector resident in HBM; no vendor library.
+ *   dl, du      n - 1 entries (sub- / super-diagonal), d: n entries, all of `dtype`;  sigma_im must be 0 for KS_F64
+ *   block_rows  0: default (64), otherwise 2...64.  A block is accepted only while max|M_p^-1 [e_first e_last]| ||M_p|| <= 1e6;
+ *               the planner shortens blocks (with backtracking) where the default split would give a singular or badly
+ *               conditioned block, and reports how many in ks_operator_tridiag_info
+ * KS_ERR_ARGUMENT: non-finite input, no admissible partition (the message names level and row), an exactly zero pivot in the
+ * direct solve, a check solve (b_i = cos(0.7 i + 0.3)) whose normwise backward error exceeds 1e-10, more than 8 levels, a
+ * multi-rank context.  Products are deterministic (bit-identical when repeated). */
+int ks_operator_tridiag_solve(ks_ctx* ctx, int64_t n, int dtype, const void* dl, const void* d, const void* du, double sigma_re,
+                              double sigma_im, int block_rows, ks_operator** out);
+/* what the planner of ks_operator_tridiag_solve made of the matrix (docs/src/index.md:234-259: the factorisation behind the
+ * LinearMap): number of levels, rows of each (level_rows: 8 entries, zero beyond `levels`), blocks shorter than the default split,
+ * the largest accepted block growth and the backward error of the check solve.  KS_ERR_ARGUMENT on any other kind of operator. */
+int ks_operator_tridiag_info(const ks_operator* op, int* levels, int64_t* level_rows /* cap 8 */, int64_t* shortened_blocks,
+                             double* max_growth, double* residual);
 int ks_operator_destroy(ks_operator* op);
 int ks_operator_size(const ks_operator* op, int64_t* n_local, int64_t* nnz, int* dtype);
 /* Device layout chosen for a stored matrix at upload (mul!(y, A, x), src/expansion.jl:121; all layouts give bit-identical y):
@@ -495,6 +515,16 @@ int ks_host_csr_plan(int64_t nrows_local, int64_t ncols, int64_t nnz, const void
                      int64_t nghost, int64_t nlow, int* plan_layout, int* ndict, double* bytes_per_nnz,
                      double* aux_bytes, int64_t* facts, int32_t* stencil_delta, int64_t* blkrow, int64_t* blkptr,
                      int64_t blk_cap, int64_t* cb_bounds, int cb_cap);
+/* The plan, the factors and the HOST apply of ks_operator_tridiag_solve without a device (docs/src/index.md:234-259: the
+ * factorize / ldiv! pair of the shift-invert recipe): x[:, k] = (T - sigma I)^-1 b[:, k] for nrhs columns (column k at b + k ldb,
+ * x + k ldx; b and x distinct), walking exactly the arrays the device kernels read, in their order.  Same refusals as the operator. */
+int ks_host_tridiag_solve(int64_t n, int dtype, const void* dl, const void* d, const void* du, double sigma_re, double sigma_im,
+                          int block_rows, int nrhs, const void* b, int64_t ldb, void* x, int64_t ldx, int* levels, double* max_growth,
+                          double* residual);
+/* ... and what ks_operator_tridiag_info would report for that input (docs/src/index.md:234-259), also without a device */
+int ks_host_tridiag_info(int64_t n, int dtype, const void* dl, const void* d, const void* du, double sigma_re, double sigma_im,
+                         int block_rows, int* levels, int64_t* level_rows /* cap 8 */, int64_t* shortened_blocks, double* max_growth,
+                         double* residual);
 /* sortschur!(H, Q, nconv, ordering)   src/run.jl:465-502 */
 int ks_host_sortschur(int dtype, void* H, int m, int n, int ldh, void* Q, int nq, int ldq, int nconv,
                       int which);

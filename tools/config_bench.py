@@ -14,6 +14,8 @@ CONFIG
   cfg4big the same at n = 5*10^6 (column = 80 MB: the ComplexF64 kernels outside the launch-bound regime)
   cfg4d   config 4 with the shift-invert operator ON THE DEVICE: (A - sigma I)^{-1} x by rocSPARSE's pivoting tridiagonal
           solver through the device-callback operator (arnoldimethod.jl_amd/extras.py); nothing n-sized crosses PCIe
+  cfg4t   the cfg4d problem with the LIBRARY's own tridiagonal shift-invert operator (ks_operator_tridiag_solve: factored once on
+          the host at upload, applied by the library's kernels in HBM; no rocSPARSE, no torch)
   cfg4h   config 4 proper: shift-invert through an opaque HOST operator (scipy splu of the shifted tridiagonal matrix),
           every product staged over PCIe (docs/src/index.md:246-249)
 Prints ONE JSON line: iterations/s, per-class {launches, avg us, GB/s, frac of 8 TB/s}, moved-bytes figure of the
@@ -59,6 +61,10 @@ def build(config, ctx):
         T = A.tocsr()
         si = extras.TridiagonalShiftInvert(T.diagonal(-1), T.diagonal(0), T.diagonal(1), sigma, ctx)
         return si.operator, n, 0, np.complex128, prm, "shift-invert ON THE DEVICE (rocSPARSE zgtsv through the device-callback operator) n=5e5"
+    if config == "cfg4t":
+        T = A.tocsr()
+        op = ks.tridiagonal_solve_operator(T.diagonal(-1), T.diagonal(0), T.diagonal(1), sigma, ctx)
+        return op, n, 0, np.complex128, prm, f"shift-invert ON THE DEVICE (ks_operator_tridiag_solve, {op.tridiag_info['levels']} levels) n=5e5"
     import scipy.sparse.linalg as spla
 
     lu = spla.splu((A - sigma * sp.identity(n)).tocsc())
