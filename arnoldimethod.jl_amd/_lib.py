@@ -128,6 +128,7 @@ PROTOTYPES = {
     "ks_col_div": [vp, i32, dbl],
     "ks_col_copy": [vp, i32, i32],
     "ks_apply": [vp, vp, i32, i32],
+    "ks_debug_apply_shifted": [vp, vp, i32, i32, dbl, dbl, dbl, i32],
     "ks_gemv_t": [vp, i32, i32, vp],
     "ks_gemv_n_sub": [vp, i32, i32, vp],
     "ks_rotate": [vp, i32, i32, i32, vp, i32],

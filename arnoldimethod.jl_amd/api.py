@@ -575,6 +575,11 @@ class ArnoldiWorkspace:
     def apply(self, A: Operator, jsrc: int, jdst: int):
         _check_op(_lib.load().ks_apply(A._h, self._h, jsrc, jdst), A)
 
+    def apply_shifted(self, A: Operator, jsrc: int, jdst: int, theta, sigma: float, cacheable: bool = False):
+        """Column jdst = sigma (A column jsrc - theta column jsrc): one Newton step of the s-step expansion (diagnostics)."""
+        theta = complex(theta)
+        _check_op(_lib.load().ks_debug_apply_shifted(A._h, self._h, jsrc, jdst, theta.real, theta.imag, float(sigma), int(bool(cacheable))), A)
+
     def gemv_t(self, j: int, jv: int) -> np.ndarray:
         h = np.empty(j, dtype=self.dtype)
         check(_lib.load().ks_gemv_t(self._h, j, jv, h.ctypes.data))

@@ -1069,6 +1069,36 @@ int ks_apply(ks_operator* A, ks_workspace* ws, int jsrc, int jdst) {
   });
 }
 
+// diagnostics: ONE Newton step of the s-step expansion, V[:, jdst] = sigma (A V[:, jsrc] - theta V[:, jsrc]), through the operator's
+// apply_shifted -- the call ks_block.hpp and ks_backend.hpp make inside a block.  cacheable_store picks the store variant of the
+// fused kernels (what the expansion decides by the block length).
+int ks_debug_apply_shifted(ks_operator* A, ks_workspace* ws, int jsrc, int jdst, double theta_re, double theta_im, double sigma,
+                           int cacheable_store) {
+  return guarded([&] {
+    KS_REQUIRE(A, KS_ERR_ARGUMENT, "null operator");
+    check_col(ws, jsrc);
+    check_col(ws, jdst);
+    KS_REQUIRE(jsrc != jdst, KS_ERR_ARGUMENT, "source and destination columns must differ");
+    KS_REQUIRE(A->n_local == ws->n && A->dtype == ws->dtype, KS_ERR_DIMENSION, "operator / workspace mismatch");
+    KS_REQUIRE(ws->dtype != KS_F64 || theta_im == 0.0, KS_ERR_ARGUMENT, "a Float64 product takes a real shift");
+    ws->ctx->use();
+    prov_drop(ws);  // the caller writes to V: the factorisation is no longer the library's own
+    materialize(ws);
+    reset_state(ws);  // (the kernels of a shifted product look at the state: a breakdown left by an earlier batch would skip them)
+    A->in_scale = 1.0;
+    const bool saved = A->shift_store_cacheable;
+    A->shift_store_cacheable = cacheable_store != 0;
+    try {
+      A->apply_shifted(ws->col(jsrc), ws->col(jdst), theta_re, theta_im, sigma, ws->ld, ws->st);
+      KS_HIP(hipStreamSynchronize(ws->ctx->stream));
+    } catch (...) {
+      A->shift_store_cacheable = saved;
+      throw;
+    }
+    A->shift_store_cacheable = saved;
+  });
+}
+
 int ks_gemv_t(ks_workspace* ws, int j, int jv, void* h_host) {
   return guarded([&] {
     check_col(ws, jv);

@@ -248,7 +248,7 @@ template <class D> struct CsrOp : ks_operator {
     return a;
   }
   void apply_shifted(const void* xv, void* yv, double tre, double tim, double sigma, int64_t ld, const DevState* st) override {
-    static const int fuse = env_int("KS_SHIFT_FUSED", 1);
+    const int fuse = env_int("KS_SHIFT_FUSED", 1);   // (read per product, like the forms of the stencil kernels: the tests switch it inside one process)
     // (every stored-matrix layout stores y = sigma (A x - theta x) itself -- the row's own x entry is one more cached load
     // -- except rows cut into chunks, whose sums are finished by a second kernel)
     const bool fused = fuse && n_local > 0 && nlong == 0;

@@ -379,6 +379,14 @@ int ks_col_div(ks_workspace* ws, int j, double s);
 int ks_col_copy(ks_workspace* ws, int dst, int src);
 /* mul!(view(V,:,jdst+1), A, view(V,:,jsrc+1))   src/expansion.jl:121 */
 int ks_apply(ks_operator* A, ks_workspace* ws, int jsrc, int jdst);
+/* Diagnostics (tests/test_gpu_shifted_product.py): one Newton step of the s-step expansion,
+ *     view(V,:,jdst+1) = sigma (A view(V,:,jsrc+1) - theta view(V,:,jsrc+1)),
+ * the shifted form of mul! at src/expansion.jl:121, through the very call the expansion makes inside a block (fused into the
+ * product's store by every stored-matrix layout, the product and one streaming pass for every other operator).  theta =
+ * (theta_re, theta_im), theta_im must be 0 for KS_F64; cacheable_store != 0 takes the cacheable store of the fused kernels
+ * (what blocks of ten and more steps use), 0 the streaming one.  Drops the provenance of the factorisation like ks_apply. */
+int ks_debug_apply_shifted(ks_operator* A, ks_workspace* ws, int jsrc, int jdst, double theta_re, double theta_im, double sigma,
+                           int cacheable_store);
 /* mul!(h, view(V,:,1:j)', view(V,:,jv+1))   src/expansion.jl:37,46,84,93   (h: j host values) */
 int ks_gemv_t(ks_workspace* ws, int j, int jv, void* h_host);
 /* mul!(view(V,:,jv+1), view(V,:,1:j), h, -1, 1)   src/expansion.jl:38,47,85,94 */
