@@ -93,6 +93,8 @@ PROTOTYPES = {
     "ks_operator_lu_layout": [vp, i32, P(i64), P(i64), P(i64), P(C.c_int)],
     "ks_operator_tridiag_solve": [vp, i64, i32, vp, vp, vp, dbl, dbl, i32, P(vp)],
     "ks_operator_tridiag_info": [vp, P(C.c_int), vp, P(i64), P(dbl), P(dbl)],
+    "ks_operator_tridiag_pencil": [vp, i64, i32, vp, vp, vp, vp, vp, vp, i32, P(vp)],
+    "ks_operator_product": [vp, i32, P(vp), P(vp)],
     "ks_operator_destroy": [vp],
     "ks_operator_size": [vp, P(i64), P(i64), P(C.c_int)],
     "ks_operator_format": [vp, P(C.c_double), P(C.c_int), P(C.c_int)],

@@ -380,6 +380,101 @@ def host_tridiagonal_solve(dl, d, du, b, sigma=0.0, block_rows: int = 0):
     return X.reshape(B.shape), info
 
 
+def _pencil_args(kdl, kd, kdu, mdl, md, mdu, sigma):
+    """The six diagonals of a tridiagonal pencil (K, M) promoted to one element type like `_tridiag_args` promotes three, and
+    T = K - sigma M formed here, in numpy: the library does no arithmetic on its inputs."""
+    both = (kdl, kd, kdu, mdl, md, mdu)
+    cplx = any(np.asarray(a).dtype.kind == "c" for a in both) or isinstance(sigma, (complex, np.complexfloating))
+    dt = np.dtype(np.complex128 if cplx else np.float64)
+    arrs = [np.ascontiguousarray(a, dtype=dt) for a in both]
+    n = arrs[1].shape[0] if arrs[1].ndim == 1 else -1
+    want = [(max(n - 1, 0),), (n,), (max(n - 1, 0),)] * 2
+    if n < 0 or [a.shape for a in arrs] != want:
+        raise DimensionMismatch(f"the diagonals of K and of M must have n entries, their off-diagonals n - 1: {[a.shape for a in arrs]}")
+    sg = dt.type(sigma)
+    K, M = arrs[:3], arrs[3:]
+    return dt, n, [np.ascontiguousarray(k - sg * m) for k, m in zip(K, M)], M
+
+
+def tridiagonal_pencil_operator(kdl, kd, kdu, mdl, md, mdu, sigma=0.0, ctx: Context | None = None, block_rows: int = 0) -> Operator:
+    """y = (K - sigma M)^-1 M x for tridiagonal K and M (sub-/main/super-diagonals of n-1, n, n-1 entries each): the operator
+    `x -> (A - sigma B) \\ (B x)` of the reference's shift-and-invert recipe for generalized problems A x = B x lambda
+    (docs/src/index.md:273-287) on a 1-D pencil -- FEM stiffness and consistent mass --, as ONE library operator
+    (`ks_operator_tridiag_pencil`): T = K - sigma M is formed here and factored once like `tridiagonal_solve_operator(T, 0)`
+    factors it, and level 0 of the elimination forms M x while it stages its right-hand side: no launch and no vector for
+    the multiplication.  The eigenvalues of the pencil closest to sigma are sigma + 1/theta.  `operator.tridiag_info` as for
+    `tridiagonal_solve_operator`."""
+    ctx = ctx or default_context()
+    lib = _lib.load()
+    dt, n, T, M = _pencil_args(kdl, kd, kdu, mdl, md, mdu, sigma)
+    ptr = lambda a: None if a.size == 0 else a.ctypes.data  # noqa: E731
+    h = C.c_void_p()
+    check(lib.ks_operator_tridiag_pencil(ctx._h, n, _dtype_code(dt), ptr(T[0]), ptr(T[1]), ptr(T[2]), ptr(M[0]), ptr(M[1]), ptr(M[2]),
+                                         int(block_rows), C.byref(h)))
+    op = Operator(ctx, h, (n, n), dt)
+    lv, sh, gr, res = C.c_int(), C.c_int64(), C.c_double(), C.c_double()
+    rows = np.zeros(8, dtype=np.int64)
+    check(lib.ks_operator_tridiag_info(h, C.byref(lv), rows.ctypes.data, C.byref(sh), C.byref(gr), C.byref(res)))
+    op.tridiag_info = dict(levels=lv.value, level_rows=[int(r) for r in rows[: lv.value]], shortened_blocks=sh.value, max_growth=gr.value,
+                           residual=res.value)
+    return op
+
+
+def host_tridiagonal_pencil_solve(kdl, kd, kdu, mdl, md, mdu, b, sigma=0.0, block_rows: int = 0):
+    """The host path of `tridiagonal_pencil_operator` (no device): the same T = K - sigma M, t = M b in the order of the device
+    kernel (md x[r], then mdl x[r-1], then mdu x[r+1]), and `host_tridiagonal_solve(T, t, sigma=0)`.  `b`: (n,) or (n, nrhs).
+    Returns (x, info) with info as `operator.tridiag_info`."""
+    dt, n, T, M = _pencil_args(kdl, kd, kdu, mdl, md, mdu, sigma)
+    B = np.asarray(b, dtype=dt)
+    cols = B.reshape(n, -1)
+    t = M[1][:, None] * cols
+    if n > 1:
+        t[1:] += M[0][:, None] * cols[:-1]
+        t[:-1] += M[2][:, None] * cols[1:]
+    return host_tridiagonal_solve(T[0], T[1], T[2], t.reshape(B.shape), sigma=0.0, block_rows=block_rows)
+
+
+class _FactorErrors:
+    """The `errors` lists of a product's callback factors seen as one list: what `_check_op` looks at, pops from and clears."""
+
+    def __init__(self, lists):
+        self._lists = lists
+
+    def __len__(self):
+        return sum(len(x) for x in self._lists)
+
+    def pop(self, i=0):
+        for x in self._lists:
+            if len(x):
+                return x.pop(i)
+        raise IndexError("pop from empty list")
+
+    def __delitem__(self, _):
+        for x in self._lists:
+            del x[:]
+
+
+def product_operator(*factors, ctx: Context | None = None) -> Operator:
+    """y = factors[0] factors[1] ... factors[-1] x, in mathematical order (the last factor is applied to x first), with every
+    intermediate vector resident in HBM (`ks_operator_product`): the composed LinearMaps of the reference's recipes for
+    generalized problems (docs/src/index.md:273-287, 325-336; `extras.generalized_shift_invert`, `extras.b_orthonormal_operator`).
+    2 to 8 `Operator`s of one size, element type and context; a factor may appear more than once.  The product keeps its factors
+    alive (`.factors`); closing it leaves them usable.  An exception raised inside a Python callback factor surfaces as that
+    exception from the call that applied the product."""
+    ctx = ctx or (factors[0].ctx if factors and isinstance(factors[0], Operator) else default_context())
+    lib = _lib.load()
+    hs = (C.c_void_p * max(len(factors), 1))(*[getattr(f, "_h", None) for f in factors])
+    h = C.c_void_p()
+    check(lib.ks_operator_product(ctx._h, len(factors), hs, C.byref(h)))
+    n, dt = factors[0].shape[0], factors[0].dtype
+    op = Operator(ctx, h, (n, n), dt, keep=tuple(factors))
+    op.factors = tuple(factors)
+    errs = [f.errors for f in factors if getattr(f, "errors", None) is not None]
+    if errs:
+        op.errors = _FactorErrors(errs)
+    return op
+
+
 def host_operator(fn, n: int, dtype=np.float64, ctx: Context | None = None) -> Operator:
     """Opaque host operator: `fn(y, x)` fills y = A*x on numpy views (a LinearMap wrapping ldiv!,
     docs/src/index.md:246-249).  Columns are staged over PCIe by the library."""

@@ -40,6 +40,7 @@ using ksd::kBlock;
 #include "ks_operators.hpp"  // ks_operator and its layouts
 #include "ks_sptrsv.hpp"     // shift-invert operator from triangular factors (sparse triangular solves)
 #include "ks_tridiag.hpp"    // tridiagonal shift-invert operator: factored once on the host (ks_tridiag_plan.hpp), applied in HBM
+#include "ks_product.hpp"    // product of operators: generalized problems composed in HBM
 #include "ks_workspace.hpp"  // ks_workspace, launch helpers, expansion, rotations
 #include "ks_block.hpp"      // s-step (block) expansion: launchers, shifts, block sizes
 #include "ks_backend.hpp"    // HipBackend, residual checks, placement search
@@ -484,6 +485,28 @@ int ks_operator_tridiag_solve(ks_ctx* ctx, int64_t n, int dtype, const void* dl,
   });
 }
 
+int ks_operator_tridiag_pencil(ks_ctx* ctx, int64_t n, int dtype, const void* dl, const void* d, const void* du, const void* mdl,
+                               const void* md, const void* mdu, int block_rows, ks_operator** out) {
+  return guarded([&] {
+    KS_REQUIRE(ctx && out, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
+    KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, "ks_operator_tridiag_pencil: single-GPU contexts only (the elimination does not shard by rows)");
+    ctx->use();
+    *out = dtype == KS_F64 ? make_tridiag_pencil<double>(ctx, n, dl, d, du, mdl, md, mdu, block_rows)
+                           : make_tridiag_pencil<cd>(ctx, n, dl, d, du, mdl, md, mdu, block_rows);
+  });
+}
+
+int ks_operator_product(ks_ctx* ctx, int nops, ks_operator* const* ops, ks_operator** out) {
+  return guarded([&] {
+    KS_REQUIRE(ctx && out && ops, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(nops >= 2 && nops <= 8, KS_ERR_ARGUMENT, "ks_operator_product: " + std::to_string(nops) + " factors (2 to 8 are supported)");
+    KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, "ks_operator_product: single-GPU contexts only (the intermediate vectors are not sharded)");
+    ctx->use();
+    *out = make_product(ctx, nops, ops);
+  });
+}
+
 int ks_operator_tridiag_info(const ks_operator* op, int* levels, int64_t* level_rows, int64_t* shortened_blocks, double* max_growth,
                              double* residual) {
   return guarded([&] {
@@ -497,7 +520,7 @@ int ks_operator_tridiag_info(const ks_operator* op, int* levels, int64_t* level_
     };
     if (auto* a = dynamic_cast<const TridiagSolveOp<double>*>(op)) fill(a);
     else if (auto* b = dynamic_cast<const TridiagSolveOp<cd>*>(op)) fill(b);
-    else throw KsError{KS_ERR_ARGUMENT, "ks_operator_tridiag_info: not an operator made by ks_operator_tridiag_solve"};
+    else throw KsError{KS_ERR_ARGUMENT, "ks_operator_tridiag_info: not an operator made by ks_operator_tridiag_solve or ks_operator_tridiag_pencil"};
   });
 }
 

@@ -3,6 +3,9 @@
 // with every vector resident in HBM.  No vendor library, no host involvement per product.
 // Part of the ONE translation unit of libkschur_hip.so: included by ks_hip.hip after ks_operators.hpp.
 //
+// The same operator with a second tridiagonal matrix in front of the solve,  y = T^-1 M x  (ks_operator_tridiag_pencil): level 0 of
+// k_td_down forms M x while it stages its right-hand side -- three more arrays, no launch and no vector more.
+//
 // Per product, on ctx->stream:  one k_td_down launch per level (the direct level included: one block, one workgroup), then one
 // k_td_up launch per level on the way back: 2 levels - 1 launches (5 at n = 5e5 and 7 at n = 1e7 with 64-row blocks).  Stream order
 // carries every dependency: no grid-wide barrier, no atomics, and the arithmetic of an entry never depends on the launch shape, so
@@ -50,10 +53,26 @@ __device__ __forceinline__ cd td_nmsub(cd a, cd b, cd c) { return cd{(c.x + a.y 
 __device__ __forceinline__ double td_sel(bool s, double a, double b) { return s ? a : b; }
 __device__ __forceinline__ cd td_sel(bool s, cd a, cd b) { return cd{s ? a.x : b.x, s ? a.y : b.y}; }
 
+// The multiplied matrix of a pencil product  y = T^-1 M x  (ks_operator_tridiag_pencil): its three diagonals, n entries each, the
+// off-diagonals padded so that row r reads entry r of all three (mdl[0] = 0, mdu[n - 1] = 0).
+// UNIFORM: every diagonal is one value (the consistent mass of a uniform mesh) -- the three values travel in the kernel arguments
+// and the product reads no band at all.
+template <class T> struct TdPencilDev {
+  const T* md = nullptr;
+  const T* mdl = nullptr;
+  const T* mdu = nullptr;
+  int uniform = 0;
+  T cd{}, cl{}, cu{};
+};
+
 // V: the level being solved; B: the level below (B.sep == nullptr at level 0: the right-hand side is src itself).
-template <class T>
-__global__ __launch_bounds__(256) void k_td_down(TdLevelDev<T> V, TdLevelDev<T> B, const T* __restrict__ src, T* __restrict__ g,
+// RHS = TdPencilDev (level 0 of a pencil product): B holds the diagonals of M and the right-hand side is M src, formed row by row
+// while it is staged -- the two neighbour entries lie in the lines the coalesced load of src[row] brings in, so the product costs no
+// launch and no vector of its own; src and g must not overlap then (a row reads its neighbours' src).
+template <class T, class RHS = TdLevelDev<T>>
+__global__ __launch_bounds__(256) void k_td_down(TdLevelDev<T> V, RHS B, const T* __restrict__ src, T* __restrict__ g,
                                                  const DevState* __restrict__ st) {
+  constexpr bool PENCIL = std::is_same<RHS, TdPencilDev<T>>::value;
   if (st && st->breakdown >= 0) return;
   extern __shared__ double2 td_lds_raw[];
   T* lds = reinterpret_cast<T*>(td_lds_raw);
@@ -67,7 +86,13 @@ __global__ __launch_bounds__(256) void k_td_down(TdLevelDev<T> V, TdLevelDev<T> 
     const int64_t row = (int64_t)V.start[p] + i;
     if (i <= V.len[p] && row < V.n) {
       T f;
-      if (B.sep == nullptr) {
+      if constexpr (PENCIL) {
+        // f = md x[r] + mdl x[r - 1] + mdu x[r + 1], in this order (api.host_tridiagonal_pencil_solve forms it the same way); nothing
+        // lies in front of the first or behind the last row of a basis column that this kernel may read
+        const T xm = row > 0 ? src[row - 1] : zero_of(T{}), xp = row + 1 < V.n ? src[row + 1] : zero_of(T{});
+        const T md = B.uniform ? B.cd : B.md[row], ml = B.uniform ? B.cl : B.mdl[row], mu = B.uniform ? B.cu : B.mdu[row];
+        f = add_(add_(mul_(md, src[row]), mul_(ml, xm)), mul_(mu, xp));
+      } else if (B.sep == nullptr) {
         f = src[row];
       } else {
         const int64_t s = B.sep[row];
@@ -186,6 +211,7 @@ template <class D> struct TridiagSolveOp : ks_operator {
   int64_t shortened = 0;
   double max_growth = 0.0, residual = 0.0;
   double bytes = 0.0;             // algorithmic bytes of one product (DESIGN: tridiagonal solve)
+  ksd::TdPencilDev<D> pencil{};   // ks_operator_tridiag_pencil: the diagonals of M (null: the plain solve)
   ~TridiagSolveOp() override {
     for (void* p : owned) (void)hipFree(p);
   }
@@ -228,17 +254,43 @@ template <class D> struct TridiagSolveOp : ks_operator {
     KS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ksd::k_td_down<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<size_t>(lds_max, 64 * 1024)));
     shortened = P.shortened; max_growth = P.max_growth; residual = P.residual;
   }
+  // y = T^-1 M x: the diagonals of M next to the plan of T (off-diagonals padded to n entries, see TdPencilDev)
+  void upload_pencil(int64_t n, const H* mdl, const H* md, const H* mdu) {
+    std::vector<H> lo((size_t)n, H(0)), di(md, md + n), up_((size_t)n, H(0));
+    for (int64_t i = 0; i + 1 < n; ++i) { lo[i + 1] = mdl[i]; up_[i] = mdu[i]; }
+    for (int64_t i = 0; i < n; ++i)
+      KS_REQUIRE(td::is_finite(lo[i]) && td::is_finite(di[i]) && td::is_finite(up_[i]), KS_ERR_ARGUMENT,
+                 "tridiagonal pencil: non-finite entry of M in row " + std::to_string(i));
+    // a uniform M (same bits in every entry of a diagonal; the pads at lo[0] and up_[n - 1] are covered by the kernel's guards)
+    // is passed by value: no arrays, no band bytes
+    bool uni = true;
+    for (int64_t i = 1; i < n && uni; ++i)
+      uni = std::memcmp(&di[i], &di[0], sizeof(H)) == 0 && (i < 2 || std::memcmp(&lo[i], &lo[1], sizeof(H)) == 0) &&
+            (i + 1 >= n || std::memcmp(&up_[i], &up_[0], sizeof(H)) == 0);
+    if (uni) {
+      pencil.uniform = 1;
+      pencil.md = upv(std::vector<H>(1, di[0]));   // (non-null: marks the pencil path)
+      std::memcpy(&pencil.cd, &di[0], sizeof(H));
+      if (n > 1) { std::memcpy(&pencil.cl, &lo[1], sizeof(H)); std::memcpy(&pencil.cu, &up_[0], sizeof(H)); }
+    } else {
+      pencil.md = upv(di); pencil.mdl = upv(lo); pencil.mdu = upv(up_);
+      bytes += 3.0 * (double)n * sizeof(D);
+    }
+    KS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ksd::k_td_down<D, ksd::TdPencilDev<D>>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<size_t>(lds_bytes(lv[0]), 64 * 1024)));
+  }
   void apply(const void* xv, void* yv, const DevState* st) override {
     ProfScope ps(ctx, KSP_SPMV, bytes);
     const D* x = static_cast<const D*>(xv);
     D* y = static_cast<D*>(yv);
     hipStream_t s = ctx->stream;
     const int nl = (int)lv.size();
+    KS_REQUIRE(!pencil.md || x != y, KS_ERR_ARGUMENT, "tridiagonal pencil: the product needs distinct x and y");
     auto gof = [&](int l) { return l == 0 ? y : scratch[l]; };
     for (int l = 0; l < nl; ++l) {
       const ksd::TdLevelDev<D>& V = lv[l];
       const int grid = (V.nblocks + ksd::kTdBlocksPerWg - 1) / ksd::kTdBlocksPerWg;
-      ksd::k_td_down<D><<<grid, kBlock, lds_bytes(V), s>>>(V, l > 0 ? lv[l - 1] : ksd::TdLevelDev<D>{}, l > 0 ? gof(l - 1) : x, gof(l), st);
+      if (l == 0 && pencil.md) ksd::k_td_down<D, ksd::TdPencilDev<D>><<<grid, kBlock, lds_bytes(V), s>>>(V, pencil, x, y, st);
+      else ksd::k_td_down<D><<<grid, kBlock, lds_bytes(V), s>>>(V, l > 0 ? lv[l - 1] : ksd::TdLevelDev<D>{}, l > 0 ? gof(l - 1) : x, gof(l), st);
       KS_HIP(hipGetLastError());
     }
     for (int l = nl - 2; l >= 0; --l) {
@@ -263,6 +315,18 @@ ks_operator* make_tridiag(ks_ctx* ctx, int64_t n, const void* dl, const void* d,
   op->nnz = 3 * n - 2;
   op->dtype = sizeof(D) == 8 ? KS_F64 : KS_C64;
   op->upload(P);
+  return op.release();
+}
+
+// y = T^-1 M x: the operator of make_tridiag on T (shift 0: the caller formed T = K - sigma M) with M's diagonals next to it
+template <class D>
+ks_operator* make_tridiag_pencil(ks_ctx* ctx, int64_t n, const void* dl, const void* d, const void* du, const void* mdl, const void* md,
+                                 const void* mdu, int block_rows) {
+  using H = typename HostT<D>::type;
+  std::unique_ptr<TridiagSolveOp<D>> op(static_cast<TridiagSolveOp<D>*>(make_tridiag<D>(ctx, n, dl, d, du, 0.0, 0.0, block_rows)));
+  KS_REQUIRE(md && (n == 1 || (mdl && mdu)), KS_ERR_ARGUMENT, "tridiagonal pencil: null diagonal of M");
+  op->upload_pencil(n, static_cast<const H*>(mdl), static_cast<const H*>(md), static_cast<const H*>(mdu));
+  op->nnz = 2 * (3 * n - 2);
   return op.release();
 }
 

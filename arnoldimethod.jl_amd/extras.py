@@ -12,6 +12,10 @@ vector resident in HBM instead of crossing PCIe twice per product.
                                                through the LIBRARY's own operator `ks_operator_lu` (hand-written
                                                synchronisation-free solve, csrc/ks_sptrsv.hpp) -- no vendor call, no torch.
 
+    generalized_shift_invert(A, B, sigma)      y = (A - sigma B)^{-1} B x for the pencil A x = B x lambda: the two operators
+                                               above composed on the device (`api.product_operator`).
+    b_orthonormal_operator(A, L)               y = L^{-1} A L^{-*} x for B = L L*: B-orthonormal Schur vectors of A.
+
 The LIBRARY's own tridiagonal shift-invert -- factored once at upload, applied by its own kernels, no rocSPARSE and no torch --
 is `api.tridiagonal_solve_operator(dl, d, du, sigma)` (`ks_operator_tridiag_solve`, csrc/ks_tridiag.hpp).
 """
@@ -143,3 +147,52 @@ def _relative_residual(M, lu) -> float:
     if not np.all(np.isfinite(y)):
         return float("inf")
     return float(np.linalg.norm(M @ y - b) / (spla.norm(M, 1) * np.linalg.norm(y) + np.linalg.norm(b)))
+
+
+def generalized_shift_invert(A, B, sigma=0.0, ctx: api.Context | None = None, **kw) -> api.Operator:
+    """`api.Operator` for y = (A - sigma B)^{-1} (B x), A and B scipy.sparse: the `ShiftAndInvert` LinearMap of the reference's
+    recipe for generalized problems A x = B x lambda (docs/src/index.md:273-287: `mul!(temp, B, x); ldiv!(y, A_lu, temp)`),
+    with the product, both triangular solves and the vector between them on the device: `sparse_shift_invert(A - sigma B, 0)`
+    (keywords are passed on to it) composed with `csr_operator(B)` by `api.product_operator`.  The eigenvalues of the pencil
+    closest to sigma are sigma + 1/theta for the largest-magnitude theta."""
+    import scipy.sparse as sp
+
+    cplx = A.dtype.kind == "c" or B.dtype.kind == "c" or isinstance(sigma, (complex, np.complexfloating))
+    dt = np.complex128 if cplx else np.float64
+    A, B = sp.csc_matrix(A, dtype=dt), sp.csr_matrix(B, dtype=dt)
+    if A.shape != B.shape:
+        raise api.DimensionMismatch(f"A and B must have one size: {A.shape}, {B.shape}")
+    ctx = ctx or api.default_context()
+    solve = sparse_shift_invert((A - dt(sigma) * B.tocsc()).tocsc(), 0.0, ctx, **kw)
+    op = api.product_operator(solve, api.csr_operator(B, ctx), ctx=ctx)
+    op.factor_residual = solve.factor_residual
+    return op
+
+
+def b_orthonormal_operator(A, L, ctx: api.Context | None = None):
+    """The reference's recipe for B-orthonormal Schur vectors (docs/src/index.md:306-352), B = L L* with a sparse
+    lower-triangular L (its Cholesky factor): returns `(operator, back)` with operator = C = L^{-1} A L^{-*} -- three device
+    factors composed by `api.product_operator`: `lu_operator(L, I)`, `csr_operator(A)`, `lu_operator(I, L*)` -- and
+    `back(Y) = L^{-*} Y` on the host.  A partial Schur decomposition C Y = Y R then gives Q = back(Y) with Q* A Q = R and
+    Q* B Q = I.
+
+    The ORDER of the two solves follows the derivation on that page, A Q = B Q R  =>  L^{-1} A Q = L* Q R  =>  (L^{-1} A L^{-*}) Y
+    = Y R with Y = L* Q.  The page's formula writes L^{-*} A L^{-1} and its code applies L^{-1} first; that coincides with the
+    derivation only where L commutes with A or, as in its example, B is diagonal (L = L*): with a bidiagonal L it leaves
+    ||Q* A Q - R|| = 0.8."""
+    import scipy.sparse as sp
+    import scipy.sparse.linalg as spla
+
+    n = A.shape[0]
+    cplx = A.dtype.kind == "c" or L.dtype.kind == "c"
+    dt = np.complex128 if cplx else np.float64
+    L = sp.csr_matrix(L, dtype=dt)
+    LH = L.conj().T.tocsr()
+    I = sp.identity(n, dtype=dt, format="csr")
+    ctx = ctx or api.default_context()
+    op = api.product_operator(api.lu_operator(L, I, ctx=ctx), api.csr_operator(sp.csr_matrix(A, dtype=dt), ctx), api.lu_operator(I, LH, ctx=ctx), ctx=ctx)
+
+    def back(Y):
+        return spla.spsolve_triangular(LH, np.asarray(Y, dtype=dt), lower=False)
+
+    return op, back

@@ -46,7 +46,7 @@ using LinearAlgebra, SparseArrays, Random
 import ArnoldiMethod
 import ArnoldiMethod: ArnoldiWorkspace, PartialSchur
 
-export HipContext, HipOperator, HipTridiagonalSolve, tridiag_info, HipWorkspace, HipBasis, HipColumn, HipColumns, hip_partialschur, hip_partialschur!, hip_partialeigen, set_sstep!, relation_breaks
+export HipContext, HipOperator, HipTridiagonalSolve, HipTridiagonalPencil, HipProduct, tridiag_info, HipWorkspace, HipBasis, HipColumn, HipColumns, hip_partialschur, hip_partialschur!, hip_partialeigen, set_sstep!, relation_breaks
 
 const LIB = get(ENV, "KSCHUR_LIB", joinpath(@__DIR__, "..", "libkschur_hip.so"))
 
@@ -222,6 +222,40 @@ function tridiag_info(A::HipOperator)
                     A.h, lv, pointer(rows), sh, gr, res))
     end
     (levels = Int(lv[]), level_rows = rows[1:lv[]], shortened_blocks = sh[], max_growth = gr[], residual = res[])
+end
+
+# Shift-invert of a TRIDIAGONAL PENCIL (the ShiftAndInvert LinearMap of docs/src/index.md:273-287 on a 1-D problem, FEM stiffness and
+# consistent mass): mul!(y, A, x) with A = T^-1 M, T = K - sigma*M formed by the caller.  T is factored like HipTridiagonalSolve
+# factors it (shift 0; tridiag_info reports the plan), and M x is formed inside the first kernel of the solve: no launch and no
+# temporary for `mul!(temp, B, x)` (ks_operator_tridiag_pencil).  The eigenvalues of the pencil nearest sigma are sigma + 1/theta.
+function HipTridiagonalPencil(ctx::HipContext, T::Tridiagonal, M::Tridiagonal; block_rows::Integer = 0)
+    E = (eltype(T) <: Complex || eltype(M) <: Complex) ? ComplexF64 : Float64
+    n = length(T.d)
+    length(M.d) == n || throw(DimensionMismatch("T and M must have one size: $(n), $(length(M.d))"))
+    a = Vector{E}(T.dl); b = Vector{E}(T.d); c = Vector{E}(T.du)
+    ma = Vector{E}(M.dl); mb = Vector{E}(M.d); mc = Vector{E}(M.du)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve a b c ma mb mc begin
+        check(ccall((:ks_operator_tridiag_pencil, LIB), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ref{Ptr{Cvoid}}),
+                    ctx.h, n, dtype_code(E), pointer(a), pointer(b), pointer(c), pointer(ma), pointer(mb), pointer(mc), Cint(block_rows), r))
+    end
+    _finish_operator(E, r[], n, ctx, nothing)
+end
+
+# Product of device operators in mathematical order, y = ops[1] * ops[2] * ... * ops[end] * x (ops[end] is applied first): the
+# composed LinearMaps of the recipes for generalized problems -- x -> (A - sigma B) \ (B x), docs/src/index.md:273-287, and
+# x -> L \ (A * (L' \ x)), docs/src/index.md:325-336 -- with the temporaries in HBM (ks_operator_product).  The library borrows the
+# factors: the product holds them (`keep`), so they outlive it.
+function HipProduct(ops::HipOperator...)
+    length(ops) >= 1 || throw(ArgumentError("HipProduct needs operators"))
+    T = eltype(ops[1]); ctx = ops[1].ctx
+    hs = Ptr{Cvoid}[A.h for A in ops]
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve hs begin
+        check(ccall((:ks_operator_product, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}), ctx.h, Cint(length(ops)), pointer(hs), r))
+    end
+    _finish_operator(T, r[], ops[1].n, ctx, ops)
 end
 
 "Device layout the library chose for a stored matrix: (bytes streamed per non-zero, dictionary size, layout code)."

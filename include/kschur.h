@@ -189,6 +189,28 @@ int ks_operator_tridiag_solve(ks_ctx* ctx, int64_t n, int dtype, const void* dl,
  * the largest accepted block growth and the backward error of the check solve.  KS_ERR_ARGUMENT on any other kind of operator. */
 int ks_operator_tridiag_info(const ks_operator* op, int* levels, int64_t* level_rows /* cap 8 */, int64_t* shortened_blocks,
                              double* max_growth, double* residual);
+/* (vi) the tridiagonal pencil, fused:  y = T^-1 M x  for tridiagonal T (factored) and M (multiplied) -- the operator
+ * x -> (A - sigma B)^-1 (B x) of the reference's shift-and-invert recipe for generalized problems A x = B x lambda
+ * (docs/src/index.md:273-287) for a 1-D pencil; the CALLER forms T = K - sigma M, the library does no arithmetic on its inputs.
+ * T is planned and factored exactly as ks_operator_tridiag_solve plans (dl, d, du) with shift 0 -- same refusals, same report
+ * through ks_operator_tridiag_info -- and level 0 of the elimination forms its right-hand side
+ * md[r] x[r] + mdl[r-1] x[r-1] + mdu[r] x[r+1] (in this order) while it stages it: no launch and no vector for M x.
+ *   mdl, mdu   n - 1 entries, md: n entries, all of `dtype` and finite;  x and y of a product must be distinct
+ * An M whose three diagonals are each one value (the consistent mass of a uniform mesh) is passed to the kernel by value: the
+ * product then streams exactly the bytes of the plain solve, otherwise 3 n sizeof(dtype) more.
+ * Eigenvalues of the pencil nearest sigma: sigma + 1/theta.  Single-GPU contexts only; deterministic like (v). */
+int ks_operator_tridiag_pencil(ks_ctx* ctx, int64_t n, int dtype, const void* dl, const void* d, const void* du, const void* mdl,
+                               const void* md, const void* mdu, int block_rows, ks_operator** out);
+/* (vii) product of operators:  y = ops[0] ops[1] ... ops[nops-1] x  in mathematical order (ops[nops-1] is applied to x first,
+ * ops[0] writes y), every intermediate vector resident in HBM -- the composed LinearMaps of the reference's recipes for
+ * generalized problems: x -> (A - sigma B)^-1 (B x), docs/src/index.md:273-287, and x -> L^-1 A L^-* x for B = L L*,
+ * docs/src/index.md:325-336.  2 <= nops <= 8; every factor non-null, made on `ctx`, of one n_local and one dtype
+ * (KS_ERR_ARGUMENT otherwise, the message names the factor); single-GPU contexts only.  The factors are BORROWED: the product
+ * never destroys them, the caller keeps them alive as long as the product is applied, and destroying the product leaves them
+ * usable; a factor may appear more than once.  The product owns at most two intermediate vectors; x is never written.  An
+ * error of a factor (a callback returning non-zero) comes out of the call that applied the product, unchanged.  The product is
+ * enqueued ahead only if every factor can be; ks_operator_size reports the sum of the factors' nnz, ks_operator_format layout -1. */
+int ks_operator_product(ks_ctx* ctx, int nops, ks_operator* const* ops, ks_operator** out);
 int ks_operator_destroy(ks_operator* op);
 int ks_operator_size(const ks_operator* op, int64_t* n_local, int64_t* nnz, int* dtype);
 /* Device layout chosen for a stored matrix at upload (mul!(y, A, x), src/expansion.jl:121; all layouts give bit-identical y):
