@@ -8,6 +8,7 @@ from ._lib import ArgumentError, CommTimeout, DimensionMismatch, HipError, QRDid
 from .api import (  # noqa: F401
     LI, LM, LR, SI, SR, ArnoldiWorkspace, Context, History, Operator, PartialSchur, Target, as_operator,
     csr_operator, default_context, dense_operator, device_operator, host_operator, lu_operator, splu_operator, tridiagonal_solve_operator, host_tridiagonal_solve, tridiagonal_pencil_operator, host_tridiagonal_pencil_solve, product_operator, partialeigen, partialschur, partialschur_, sstep_partition, vtype,
+    DeviceVectors, gram, residuals, schur_vectors, vector_residuals,
 )
 from . import matrices  # noqa: F401
 # `extras` (ready-made device operators on the callback seam; needs torch + rocSPARSE) is imported on demand:
@@ -17,4 +18,5 @@ __all__ = [
     "partialschur", "partialschur_", "partialeigen", "ArnoldiWorkspace", "PartialSchur", "History",
     "LM", "LR", "SR", "LI", "SI", "Context", "Operator", "csr_operator", "dense_operator", "host_operator", "device_operator", "lu_operator", "splu_operator", "tridiagonal_solve_operator", "host_tridiagonal_solve", "tridiagonal_pencil_operator", "host_tridiagonal_pencil_solve", "product_operator", "as_operator",
     "ArgumentError", "DimensionMismatch", "CommTimeout", "matrices", "sstep_partition",
+    "DeviceVectors", "residuals", "vector_residuals", "gram", "schur_vectors",
 ]

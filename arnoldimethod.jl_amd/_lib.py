@@ -147,6 +147,16 @@ PROTOTYPES = {
     "ks_profile_get": [vp, i32, vp, vp, vp],
     "ks_residual_norms": [vp, vp, i32, P(dbl), P(dbl)],
     "ks_arnoldi_relation": [vp, vp, i32, P(dbl), P(dbl)],
+    "ks_vectors_create": [vp, i64, i32, i32, P(vp)],
+    "ks_vectors_destroy": [vp],
+    "ks_vectors_dims": [vp, P(i64), P(C.c_int), P(C.c_int), P(i64)],
+    "ks_vectors_upload": [vp, i32, i32, vp, i64],
+    "ks_vectors_download": [vp, i32, i32, vp, i64],
+    "ks_vectors_col_ptr": [vp, i32, P(vp)],
+    "ks_basis_times_device": [vp, i32, i32, vp, i32, i32, vp],
+    "ks_vectors_apply": [vp, vp, vp],
+    "ks_vectors_residuals": [vp, vp, vp, i32, P(dbl), P(dbl)],
+    "ks_vectors_gram": [vp, vp, vp, i32],
     "ks_host_schurfact": [i32, vp, i32, i32, i32, i32, i32, vp, i32, i32],
     "ks_host_restart_step": [i32, vp, i32, vp, i32, i32, i32, i32, i32, dbl, i32, P(C.c_int), P(C.c_int), P(C.c_int), vp, vp, vp],
     "ks_host_sortschur": [i32, vp, i32, i32, i32, vp, i32, i32, i32, i32],

@@ -697,6 +697,17 @@ class ArnoldiWorkspace:
         check(_lib.load().ks_basis_times(self._h, c, Yf.shape[1], Yf.ctypes.data, Yf.shape[0], _dtype_code(ydt), out.ctypes.data, self.n))
         return out
 
+    def basis_times_device(self, c: int, Y) -> "DeviceVectors":
+        """`basis_times` with the product left in HBM (`ks_basis_times_device`): no copy of the vectors to the host."""
+        Y = np.asarray(Y)
+        if Y.ndim != 2 or Y.shape[0] != c or Y.shape[1] < 1:
+            raise DimensionMismatch(f"coefficients must be ({c}, r) with r >= 1, got {Y.shape}")
+        ydt = np.complex128 if (Y.dtype.kind == "c" or self.dtype.kind == "c") else np.float64
+        Yf = np.asfortranarray(Y.astype(ydt))
+        out = DeviceVectors(self.n, Yf.shape[1], ydt, self.ctx)
+        check(_lib.load().ks_basis_times_device(self._h, c, Yf.shape[1], Yf.ctypes.data, Yf.shape[0], _dtype_code(ydt), out._h))
+        return out
+
     def orthogonalize(self, j: int) -> bool:
         ok = C.c_int()
         check(_lib.load().ks_orthogonalize(self._h, j, C.byref(ok)))
@@ -991,15 +1002,177 @@ def partialschur_(A, arnoldi: ArnoldiWorkspace, start_from=1, initialize=None, n
     return _run(op, arnoldi, nev, which, tol, mindim, maxdim, restarts, start_from, initialize, v1)
 
 
-def partialeigen(P: PartialSchur):
+def partialeigen(P: PartialSchur, device: bool = False):
     """partialeigen(P) -> (eigenvalues, eigenvectors), src/eigvals.jl:92-95: LAPACK `eigen(R)` on the
-    host (nev x nev) and the tall-skinny product Q*vecs on the device."""
+    host (nev x nev) and the tall-skinny product Q*vecs on the device.  `device=True` leaves the eigenvectors in HBM and
+    returns them as `DeviceVectors` (`ks_basis_times_device`) for `residuals` / `gram` / `DeviceVectors.apply`."""
     import scipy.linalg as sla
 
     k = P.nconverged
     if k == 0:
+        if device:
+            raise ArgumentError("no converged eigenvalues: there are no vectors to keep on the device")
         return np.zeros(0, dtype=np.complex128), np.zeros((P.workspace.n, 0), dtype=np.complex128)
     vals, vecs = sla.eig(np.array(P.R))
     if P.workspace.dtype.kind == "f" and np.all(vals.imag == 0):
         vecs = vecs.real
+    if device:
+        return vals, P.workspace.basis_times_device(k, vecs)
     return vals, P.workspace.basis_times(k, vecs)
+
+
+# ------------------------------------------------------------------ device-resident vectors
+class DeviceVectors:
+    """n x r vectors in HBM (`ks_vectors`, include/kschur.h): operators are applied to them column by column and their residuals
+    and Gram matrices come back as a few small numbers, so the recipes of the reference's "Bringing problems to standard form"
+    stay on the device through "translate back" (docs/src/index.md:347) and the checks against the ORIGINAL matrices
+    (docs/src/index.md:258, 302, 350-351).  1 <= r <= 64."""
+
+    def __init__(self, n: int, ncols: int, dtype=np.float64, ctx: Context | None = None):
+        self.ctx = ctx or default_context()
+        self.dtype = np.dtype(vtype(np.empty(0, dtype=dtype)))
+        self.shape = (int(n), int(ncols))
+        h = C.c_void_p()
+        check(_lib.load().ks_vectors_create(self.ctx._h, int(n), int(ncols), _dtype_code(self.dtype), C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def from_host(cls, M, ctx: Context | None = None) -> "DeviceVectors":
+        M = np.asarray(M)
+        if M.ndim != 2:
+            raise DimensionMismatch(f"vectors must be a matrix (n, r), got shape {M.shape}")
+        X = cls(M.shape[0], M.shape[1], vtype(M), ctx)
+        Mf = np.asfortranarray(M.astype(X.dtype))
+        if Mf.shape[0]:
+            check(_lib.load().ks_vectors_upload(X._h, 0, Mf.shape[1], Mf.ctypes.data, Mf.shape[0]))
+        return X
+
+    def download(self) -> np.ndarray:
+        n, r = self.shape
+        out = np.empty((n, r), dtype=self.dtype, order="F")
+        if n:
+            check(_lib.load().ks_vectors_download(self._h, 0, r, out.ctypes.data, n))
+        return out
+
+    @property
+    def ld(self) -> int:
+        """Leading dimension in elements (a multiple of 64; rows n .. ld-1 of every column are zero)."""
+        ld = C.c_int64()
+        check(_lib.load().ks_vectors_dims(self._h, None, None, None, C.byref(ld)))
+        return ld.value
+
+    def col_ptr(self, j: int) -> int:
+        """Device address of column j (`ld` elements, the first n of them the column)."""
+        p = C.c_void_p()
+        check(_lib.load().ks_vectors_col_ptr(self._h, int(j), C.byref(p)))
+        return p.value or 0
+
+    def apply(self, op: Operator) -> "DeviceVectors":
+        """op applied to every column, as new vectors; a Float64 operator on ComplexF64 vectors acts on the real and the imaginary
+        part.  An exception raised inside a Python callback operator surfaces as that exception."""
+        _check_apply(op, self)
+        out = DeviceVectors(self.shape[0], self.shape[1], self.dtype, self.ctx)
+        _check_op(_lib.load().ks_vectors_apply(op._h, self._h, out._h), op)
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            _lib.load().ks_vectors_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _check_apply(op, X):
+    """The argument checks of `DeviceVectors.apply` / `residuals`, before any device call."""
+    if not isinstance(op, Operator):
+        raise ArgumentError(f"expected an Operator, got {type(op).__name__}")
+    if not isinstance(X, DeviceVectors):
+        raise ArgumentError(f"expected DeviceVectors, got {type(X).__name__}")
+    if op.shape[0] != X.shape[0]:
+        raise DimensionMismatch(f"the operator has {op.shape[0]} rows, the vectors have {X.shape[0]}")
+    if op.ctx is not X.ctx:
+        raise ArgumentError("the operator and the vectors live on different contexts")
+    if op.dtype.kind == "c" and X.dtype.kind != "c":
+        raise ArgumentError("a ComplexF64 operator needs ComplexF64 vectors")
+
+
+def _check_pair(X, Y, same_cols: bool):
+    for V in (X, Y):
+        if not isinstance(V, DeviceVectors):
+            raise ArgumentError(f"expected DeviceVectors, got {type(V).__name__}")
+    if X.shape[0] != Y.shape[0] or (same_cols and X.shape[1] != Y.shape[1]):
+        raise DimensionMismatch(f"the vectors have shapes {X.shape} and {Y.shape}")
+    if X.dtype != Y.dtype:
+        raise ArgumentError(f"the vectors have element types {X.dtype} and {Y.dtype}")
+    if X.ctx is not Y.ctx:
+        raise ArgumentError("the vectors live on different contexts")
+
+
+def residual_coefficients(lam_or_C, r: int, dtype) -> np.ndarray:
+    """The r x r coefficient block of `residuals` in the vectors' element type: a 1-D `lam` (r eigenvalues) becomes diag(lam), a 2-D
+    block (R of a Schur decomposition, or a block-diagonal matrix whose real 2 x 2 blocks carry conjugate pairs) is taken as it
+    is.  Complex coefficients with Float64 vectors are an ArgumentError (use the complex vectors of `partialeigen`)."""
+    dt = np.dtype(vtype(np.empty(0, dtype=dtype)))
+    Cm = np.asarray(lam_or_C)
+    if Cm.ndim == 1:
+        if Cm.shape[0] != r:
+            raise DimensionMismatch(f"{Cm.shape[0]} eigenvalues for {r} vectors")
+        Cm = np.diag(Cm)
+    elif Cm.ndim != 2 or Cm.shape != (r, r):
+        raise DimensionMismatch(f"the coefficient block must be ({r}, {r}), got {Cm.shape}")
+    if Cm.dtype.kind == "c" and dt.kind != "c":
+        raise ArgumentError("complex coefficients need ComplexF64 vectors")
+    return np.asfortranarray(Cm.astype(dt))
+
+
+def residuals(A: Operator, X: DeviceVectors, lam_or_C, B: Operator | None = None):
+    """(resid, bnorm) with resid[i] = ||A X[:, i] - sum_j (B X)[:, j] C[j, i]||_2 and bnorm[i] = ||(B X)[:, i]||_2, evaluated on the
+    device against the ORIGINAL `A` (and `B`; None: the identity): `lam_or_C` is a vector of eigenvalues (A x = x lambda,
+    A x = B x lambda, docs/src/index.md:258, 302) or a square block such as R (A Q = B Q R).  Only 2 r numbers cross PCIe."""
+    _check_apply(A, X)
+    if B is not None:
+        _check_apply(B, X)
+    Cm = residual_coefficients(lam_or_C, X.shape[1], X.dtype)
+    AX = X.apply(A)
+    BX = X if B is None else X.apply(B)
+    r = X.shape[1]
+    resid, bnorm = np.zeros(r), np.zeros(r)
+    check(_lib.load().ks_vectors_residuals(AX._h, BX._h, Cm.ctypes.data, r, resid.ctypes.data_as(C.POINTER(C.c_double)),
+                                           bnorm.ctypes.data_as(C.POINTER(C.c_double))))
+    AX.close()
+    if BX is not X:
+        BX.close()
+    return resid, bnorm
+
+
+def vector_residuals(AX: DeviceVectors, BX: DeviceVectors, lam_or_C):
+    """`residuals` for products that already exist: (||AX[:, i] - sum_j BX[:, j] C[j, i]||_2, ||BX[:, i]||_2); BX may be AX."""
+    _check_pair(AX, BX, True)
+    Cm = residual_coefficients(lam_or_C, AX.shape[1], AX.dtype)
+    r = AX.shape[1]
+    resid, bnorm = np.zeros(r), np.zeros(r)
+    check(_lib.load().ks_vectors_residuals(AX._h, BX._h, Cm.ctypes.data, r, resid.ctypes.data_as(C.POINTER(C.c_double)),
+                                           bnorm.ctypes.data_as(C.POINTER(C.c_double))))
+    return resid, bnorm
+
+
+def gram(X: DeviceVectors, Y: DeviceVectors) -> np.ndarray:
+    """X^H Y (r_x x r_y) computed on the device: Q* B Q - I and Q* A Q - R of docs/src/index.md:350-351 from Q and Q.apply(...)."""
+    _check_pair(X, Y, False)
+    G = np.zeros((X.shape[1], Y.shape[1]), dtype=X.dtype, order="F")
+    check(_lib.load().ks_vectors_gram(X._h, Y._h, G.ctypes.data, X.shape[1]))
+    return G
+
+
+def schur_vectors(P: PartialSchur) -> DeviceVectors:
+    """A device copy of the Schur vectors Q of `P` (the basis times the identity): `schur_vectors(P).apply(back.operator)` is the
+    back-transformation of `extras.b_orthonormal_operator` without the host."""
+    k = P.nconverged
+    if k == 0:
+        raise ArgumentError("no converged eigenvalues: there are no vectors to keep on the device")
+    return P.workspace.basis_times_device(k, np.eye(k, dtype=P.workspace.dtype))

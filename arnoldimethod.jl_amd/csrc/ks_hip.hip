@@ -44,6 +44,7 @@ using ksd::kBlock;
 #include "ks_workspace.hpp"  // ks_workspace, launch helpers, expansion, rotations
 #include "ks_block.hpp"      // s-step (block) expansion: launchers, shifts, block sizes
 #include "ks_backend.hpp"    // HipBackend, residual checks, placement search
+#include "ks_vectors.hpp"    // n x r vectors in HBM: back-transformation, column residuals and Gram matrices without a download
 
 // ================================================================================================
 // C ABI
@@ -1456,6 +1457,158 @@ int ks_arnoldi_relation(ks_operator* A, ks_workspace* ws, int k, double* resid, 
     dispatch_dtype(ws->dtype, [&](auto tag) {
       using T = decltype(tag);
       relation_norms<T>(A, ws, k, k + 1, static_cast<const T*>(ws->H), ws->maxdim + 1, resid, orth);
+    });
+  });
+}
+
+// ---- device-resident vectors (ks_vectors.hpp) ------------------------------------------------------------
+int ks_vectors_create(ks_ctx* ctx, int64_t n_local, int ncols, int dtype, ks_vectors** out) {
+  return guarded([&] {
+    KS_REQUIRE(ctx && out, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
+    KS_REQUIRE(n_local >= 0, KS_ERR_ARGUMENT, "negative size");
+    KS_REQUIRE(ncols >= 1 && ncols <= kVecMaxCols, KS_ERR_ARGUMENT, "ks_vectors_create: " + std::to_string(ncols) + " columns (1 to 64 are supported)");
+    KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, "ks_vectors_create: single-GPU contexts only (the vectors are not sharded)");
+    ctx->use();
+    *out = make_vectors(ctx, n_local, ncols, dtype);
+  });
+}
+
+int ks_vectors_destroy(ks_vectors* v) {
+  return guarded([&] {
+    if (!v) return;
+    (void)hipSetDevice(v->ctx->device);
+    (void)hipStreamSynchronize(v->ctx->stream);
+    delete v;
+  });
+}
+
+int ks_vectors_dims(const ks_vectors* v, int64_t* n_local, int* ncols, int* dtype, int64_t* ld) {
+  return guarded([&] {
+    KS_REQUIRE(v, KS_ERR_ARGUMENT, "null vectors");
+    if (n_local) *n_local = v->n;
+    if (ncols) *ncols = v->ncols;
+    if (dtype) *dtype = v->dtype;
+    if (ld) *ld = v->ld;
+  });
+}
+
+int ks_vectors_upload(ks_vectors* v, int j0, int ncols, const void* host, int64_t ldhost) {
+  return guarded([&] {
+    KS_REQUIRE(v && host, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(j0 >= 0 && ncols >= 0 && j0 + ncols <= v->ncols, KS_ERR_ARGUMENT, "column range out of bounds");
+    KS_REQUIRE(ldhost >= v->n, KS_ERR_ARGUMENT, "ldhost too small");
+    if (ncols == 0 || v->n == 0) return;
+    v->ctx->use();
+    KS_HIP(hipMemcpy2DAsync(v->col(j0), (size_t)v->ld * v->esz, host, (size_t)ldhost * v->esz, (size_t)v->n * v->esz, (size_t)ncols,
+                            hipMemcpyHostToDevice, v->ctx->stream));
+    KS_HIP(hipStreamSynchronize(v->ctx->stream));
+  });
+}
+
+int ks_vectors_download(const ks_vectors* v, int j0, int ncols, void* host, int64_t ldhost) {
+  return guarded([&] {
+    KS_REQUIRE(v && host, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(j0 >= 0 && ncols >= 0 && j0 + ncols <= v->ncols, KS_ERR_ARGUMENT, "column range out of bounds");
+    KS_REQUIRE(ldhost >= v->n, KS_ERR_ARGUMENT, "ldhost too small");
+    if (ncols == 0 || v->n == 0) return;
+    v->ctx->use();
+    KS_HIP(hipMemcpy2DAsync(host, (size_t)ldhost * v->esz, v->col(j0), (size_t)v->ld * v->esz, (size_t)v->n * v->esz, (size_t)ncols,
+                            hipMemcpyDeviceToHost, v->ctx->stream));
+    KS_HIP(hipStreamSynchronize(v->ctx->stream));
+  });
+}
+
+int ks_vectors_col_ptr(ks_vectors* v, int j, void** dev_ptr) {
+  return guarded([&] {
+    KS_REQUIRE(v && dev_ptr, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(j >= 0 && j < v->ncols, KS_ERR_ARGUMENT, "column index out of range");
+    *dev_ptr = v->col(j);
+  });
+}
+
+int ks_basis_times_device(ks_workspace* ws, int c, int r, const void* Y_host, int ldy, int ydtype, ks_vectors* out) {
+  return guarded([&] {
+    KS_REQUIRE(ws && Y_host && out, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(c >= 1 && r >= 1 && c <= ws->maxdim + 1 && ldy >= c, KS_ERR_ARGUMENT, "bad shape");
+    KS_REQUIRE(ydtype == KS_C64 || ydtype == ws->dtype, KS_ERR_ARGUMENT, "coefficient dtype must be complex or match the basis");
+    KS_REQUIRE(out->ctx == ws->ctx, KS_ERR_ARGUMENT, "ks_basis_times_device: the vectors live on another context than the workspace");
+    KS_REQUIRE(out->n == ws->n && out->ncols >= r, KS_ERR_ARGUMENT,
+               "ks_basis_times_device: the vectors are (" + std::to_string(out->n) + ", " + std::to_string(out->ncols) + "), the product is (" +
+                   std::to_string(ws->n) + ", " + std::to_string(r) + ")");
+    KS_REQUIRE(out->dtype == ydtype, KS_ERR_ARGUMENT, "ks_basis_times_device: the vectors do not have the element type of the coefficients");
+    ws->ctx->use();
+    materialize(ws);
+    if (ws->n == 0) return;
+    hipStream_t s = ws->ctx->stream;
+    const size_t yes = ydtype == KS_F64 ? 8 : 16;
+    const size_t smem = (size_t)c * r * yes;
+    // coefficients -> device (contiguous, ld = c)
+    std::vector<char> yc(smem);
+    for (int jj = 0; jj < r; ++jj)
+      std::memcpy(yc.data() + (size_t)jj * c * yes, static_cast<const char*>(Y_host) + (size_t)jj * ldy * yes, (size_t)c * yes);
+    void* yd = ws->ensure_tmp2(smem);
+    KS_HIP(hipMemcpyAsync(yd, yc.data(), smem, hipMemcpyHostToDevice, s));
+    if (ws->dtype == KS_F64 && ydtype == KS_F64)
+      gemm_tall_chunked<double, double>(ws, (const double*)ws->V, c, r, (const double*)yd, c, (double*)out->data, out->ld);
+    else if (ws->dtype == KS_F64)
+      gemm_tall_chunked<double, cd>(ws, (const double*)ws->V, c, r, (const cd*)yd, c, (cd*)out->data, out->ld);
+    else
+      gemm_tall_chunked<cd, cd>(ws, (const cd*)ws->V, c, r, (const cd*)yd, c, (cd*)out->data, out->ld);
+    KS_HIP(hipStreamSynchronize(s));
+  });
+}
+
+int ks_vectors_apply(ks_operator* op, const ks_vectors* in, ks_vectors* out) {
+  return guarded([&] {
+    KS_REQUIRE(op && in && out, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(out != in, KS_ERR_ARGUMENT, "ks_vectors_apply: the result must not be the input");
+    vec_check_pair("ks_vectors_apply", in, out, true);
+    KS_REQUIRE(op->ctx == in->ctx, KS_ERR_ARGUMENT, "ks_vectors_apply: the operator lives on another context than the vectors");
+    KS_REQUIRE(op->n_local == in->n, KS_ERR_ARGUMENT,
+               "ks_vectors_apply: the operator has " + std::to_string(op->n_local) + " rows, the vectors have " + std::to_string(in->n));
+    KS_REQUIRE(op->dtype == in->dtype || op->dtype == KS_F64, KS_ERR_ARGUMENT, "ks_vectors_apply: a ComplexF64 operator needs ComplexF64 vectors");
+    in->ctx->use();
+    vectors_apply(op, in, out);
+    KS_HIP(hipStreamSynchronize(in->ctx->stream));
+    in->ctx->check_comm();
+  });
+}
+
+int ks_vectors_residuals(const ks_vectors* AX, const ks_vectors* BX, const void* C_host, int ldc, double* resid, double* bnorm) {
+  return guarded([&] {
+    KS_REQUIRE(AX && BX && C_host && resid && bnorm, KS_ERR_ARGUMENT, "null argument");
+    vec_check_pair("ks_vectors_residuals", AX, BX, true);
+    KS_REQUIRE(ldc >= AX->ncols, KS_ERR_ARGUMENT, "ks_vectors_residuals: leading dimension smaller than the coefficient block");
+    AX->ctx->use();
+    std::vector<double> r2(AX->ncols, 0.0), b2(AX->ncols, 0.0);
+    if (AX->n > 0)
+      dispatch_dtype(AX->dtype, [&](auto tag) {
+        using T = decltype(tag);
+        vectors_residuals<T>(AX, BX, static_cast<const T*>(C_host), ldc, r2.data(), b2.data());
+      });
+    for (int i = 0; i < AX->ncols; ++i) {  // (the roots on the host: correctly rounded)
+      resid[i] = std::sqrt(r2[i]);
+      bnorm[i] = std::sqrt(b2[i]);
+    }
+  });
+}
+
+int ks_vectors_gram(const ks_vectors* X, const ks_vectors* Y, void* G_host, int ldg) {
+  return guarded([&] {
+    KS_REQUIRE(X && Y && G_host, KS_ERR_ARGUMENT, "null argument");
+    vec_check_pair("ks_vectors_gram", X, Y, false);
+    KS_REQUIRE(ldg >= X->ncols, KS_ERR_ARGUMENT, "ks_vectors_gram: leading dimension smaller than the result");
+    X->ctx->use();
+    dispatch_dtype(X->dtype, [&](auto tag) {
+      using T = decltype(tag);
+      T* G = static_cast<T*>(G_host);
+      if (X->n == 0) {
+        for (int j = 0; j < Y->ncols; ++j)
+          for (int i = 0; i < X->ncols; ++i) G[i + (size_t)j * ldg] = T(0);
+        return;
+      }
+      vectors_gram<T>(X, Y, G, ldg);
     });
   });
 }

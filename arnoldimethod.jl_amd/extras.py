@@ -173,7 +173,8 @@ def b_orthonormal_operator(A, L, ctx: api.Context | None = None):
     """The reference's recipe for B-orthonormal Schur vectors (docs/src/index.md:306-352), B = L L* with a sparse
     lower-triangular L (its Cholesky factor): returns `(operator, back)` with operator = C = L^{-1} A L^{-*} -- three device
     factors composed by `api.product_operator`: `lu_operator(L, I)`, `csr_operator(A)`, `lu_operator(I, L*)` -- and
-    `back(Y) = L^{-*} Y` on the host.  A partial Schur decomposition C Y = Y R then gives Q = back(Y) with Q* A Q = R and
+    `back(Y) = L^{-*} Y` on the host (`back.operator`: the device factor L^{-*} itself, for vectors that stay in HBM:
+    `api.schur_vectors(P).apply(back.operator)`).  A partial Schur decomposition C Y = Y R then gives Q = back(Y) with Q* A Q = R and
     Q* B Q = I.
 
     The ORDER of the two solves follows the derivation on that page, A Q = B Q R  =>  L^{-1} A Q = L* Q R  =>  (L^{-1} A L^{-*}) Y
@@ -195,4 +196,6 @@ def b_orthonormal_operator(A, L, ctx: api.Context | None = None):
     def back(Y):
         return spla.spsolve_triangular(LH, np.asarray(Y, dtype=dt), lower=False)
 
+    # the same back-transformation on the device: Q = api.schur_vectors(P).apply(back.operator)
+    back.operator = op.factors[2]
     return op, back

@@ -519,6 +519,40 @@ int ks_residual_norms(ks_operator* A, ks_workspace* ws, int ncols, double* resid
 /* Arnoldi relation check ||A V_k - V_{k+1} H_k||_F and ||V'V - I||_F (test/expansion.jl:24-31). */
 int ks_arnoldi_relation(ks_operator* A, ks_workspace* ws, int k, double* resid, double* orth);
 
+/* ---- device-resident vectors ---------------------------------------------------------------
+ * n_local x ncols vectors in HBM that operators are applied to and whose residuals and Gram matrices come back as a few small
+ * numbers: the last two steps of the reference's recipes -- "translate back to the original problem" (Q = L^-* Y,
+ * docs/src/index.md:347) and the checks A x = x lambda, A x = B x lambda, Q* A Q = R, Q* B Q = I against the ORIGINAL matrices
+ * (docs/src/index.md:258, 302, 350-351) -- without a copy of the vectors to the host.  Column-major, leading dimension `ld` a
+ * multiple of 64 elements, zero-filled once; every call writes rows < n_local only, so the pad rows stay zero (the stored-matrix
+ * kernels may read the pad rows of their input).  1 <= ncols <= 64; single-GPU contexts only; n_local = 0 is legal and every
+ * call on such vectors is a no-op.  Every call that touches device memory synchronises the context's stream before it returns. */
+typedef struct ks_vectors ks_vectors;
+int ks_vectors_create(ks_ctx* ctx, int64_t n_local, int ncols, int dtype, ks_vectors** out);
+int ks_vectors_destroy(ks_vectors* v);
+int ks_vectors_dims(const ks_vectors* v, int64_t* n_local, int* ncols, int* dtype, int64_t* ld);
+/* columns j0 .. j0+ncols-1 from / to a host matrix, column-major with leading dimension ldhost >= n_local */
+int ks_vectors_upload(ks_vectors* v, int j0, int ncols, const void* host, int64_t ldhost);
+int ks_vectors_download(const ks_vectors* v, int j0, int ncols, void* host, int64_t ldhost);
+int ks_vectors_col_ptr(ks_vectors* v, int j, void** dev_ptr);
+/* ks_basis_times with the result left on the device: out[:, 0:r) = V[:, 0:c) * Y[0:c, 0:r).  `out` has n_local of the workspace,
+ * at least r columns and the element type `ydtype` (a real basis times complex coefficients gives complex vectors). */
+int ks_basis_times_device(ks_workspace* ws, int c, int r, const void* Y_host, int ldy, int ydtype, ks_vectors* out);
+/* out[:, i] = op in[:, i] for every column, any operator kind (callbacks and products included); out != in, same shape, element
+ * type and context (KS_ERR_ARGUMENT otherwise).  An error of the operator (a callback returning non-zero) comes out unchanged.
+ * A Float64 operator on ComplexF64 vectors -- a real problem with complex-conjugate Ritz pairs -- is applied to the real and to the
+ * imaginary part, each bit-identical to the operator applied to that part alone; a ComplexF64 operator on Float64 vectors is
+ * KS_ERR_ARGUMENT. */
+int ks_vectors_apply(ks_operator* op, const ks_vectors* in, ks_vectors* out);
+/* resid[i] = || AX[:, i] - sum_j BX[:, j] C[j, i] ||_2 and bnorm[i] = || BX[:, i] ||_2, i < r = ncols, in ONE sweep over AX and BX
+ * (r r sizeof(element) <= 48 KiB and r <= 56 / 40 columns for Float64 / ComplexF64; wider blocks sweep BX once per chunk of
+ * columns).  C is r x r in the vectors' element type, host, column-major ldc: diagonal for the eigenpair check A x - lambda B x,
+ * R for the Schur check A Q - B Q R.  BX may be AX's own object.  Deterministic: the same bits every time; the square roots are
+ * taken on the host. */
+int ks_vectors_residuals(const ks_vectors* AX, const ks_vectors* BX, const void* C_host, int ldc, double* resid, double* bnorm);
+/* G = X^H Y (ncols(X) x ncols(Y), host, column-major ldg): Q* B Q - I and Q* A Q - R.  One download, one synchronisation. */
+int ks_vectors_gram(const ks_vectors* X, const ks_vectors* Y, void* G_host, int ldg);
+
 /* ---- host small dense kernels, exported for the host-logic tests (no device needed) ------ */
 /* local_schurfact!(H, start, to, Q)   src/schurfact.jl:393-538; H is m x n column-major. */
 int ks_host_schurfact(int dtype, void* H, int m, int n, int ldh, int start, int to, void* Q, int nq,
