@@ -475,6 +475,79 @@ def product_operator(*factors, ctx: Context | None = None) -> Operator:
     return op
 
 
+def _grid_args(shape, taps, potential, dtype):
+    """(dtype, dims, taps, potential or None) of a grid operator.  The element type is promoted like `_tridiag_args` promotes
+    (ComplexF64 as soon as the taps or the potential are complex) unless `dtype` pins it; a pinned Float64 refuses imaginary parts."""
+    try:
+        dims = np.atleast_1d(np.asarray(shape, dtype=np.int64))
+    except (TypeError, ValueError, OverflowError) as e:
+        raise ArgumentError(f"shape must hold 1 to 3 integer extents: {shape!r}") from e
+    if dims.ndim != 1 or not 1 <= dims.size <= 3:
+        raise ArgumentError(f"a grid has 1, 2 or 3 dimensions (ndim), shape = {shape!r}")
+    ndim = int(dims.size)
+    t, v = np.asarray(taps), None if potential is None else np.asarray(potential)
+    cplx = t.dtype.kind == "c" or (v is not None and v.dtype.kind == "c")
+    dt = np.dtype(np.complex128 if cplx else np.float64) if dtype is None else np.dtype(dtype)
+    if dt not in (np.dtype(np.float64), np.dtype(np.complex128)):
+        raise ArgumentError(f"element type must be float64 or complex128, not {dt}")
+    if dt.kind == "f" and cplx and (np.any(t.imag != 0) or (v is not None and np.any(v.imag != 0))):
+        raise ArgumentError("taps or potential have an imaginary part but the element type is Float64 (KS_F64)")
+    if t.shape != (2 * ndim + 1,):
+        raise DimensionMismatch(f"a {ndim}-D grid takes {2 * ndim + 1} taps in ascending column order, got shape {t.shape}")
+    t = np.ascontiguousarray(t.real if dt.kind == "f" else t, dtype=dt)
+    if v is not None:
+        n = math.prod(int(d) for d in dims)
+        # (an extent < 1 is the library's refusal to make: it checks the extents before it reads the potential)
+        if np.all(dims >= 1) and v.shape != (n,) and v.shape != tuple(int(d) for d in dims[::-1]):
+            raise DimensionMismatch(f"potential must have shape {tuple(int(d) for d in dims[::-1])} (C order, x fastest) or ({n},), got {v.shape}")
+        v = np.ascontiguousarray((v.real if dt.kind == "f" else v).reshape(-1), dtype=dt)
+    return dt, np.ascontiguousarray(dims), t, v
+
+
+def grid_operator(shape, taps, potential=None, dtype=None, ctx: Context | None = None) -> Operator:
+    """Matrix-free operator of a constant-coefficient 3-, 5- or 7-point stencil plus a per-point diagonal term on a grid
+    (`ks_operator_grid`): mul!(y, A, x), src/expansion.jl:121, for A = -Laplacian + V(x) and its kin with nothing stored per
+    non-zero -- 24 bytes per row and product in Float64 (16 without a potential) where a stored matrix with a varying diagonal
+    streams about 100.
+
+    `shape` = (nx,), (nx, ny) or (nx, ny, nz), x fastest: row r = ix + nx (iy + ny iz).  `taps`: 2 ndim + 1 values in ascending
+    column order, [-z, -y, -x, centre, +x, +y, +z] in 3-D; a tap whose neighbour lies outside the grid is absent (no wrap-around).
+    `potential`: None, or n values added to the centre tap -- flat in row order, or an array of shape (nz, ny, nx) / (ny, nx) in C
+    order (so that `potential.ravel()` is the row order).  The operator is exactly the matrix `host_grid_matrix` returns, and its
+    products have the bits `csr_operator` of that matrix gives.  `operator.grid_info`: shape, taps, has_potential, bytes_per_row."""
+    ctx = ctx or default_context()
+    lib = _lib.load()
+    dt, dims, t, v = _grid_args(shape, taps, potential, dtype)
+    h = C.c_void_p()
+    check(lib.ks_operator_grid(ctx._h, int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data, None if v is None else v.ctypes.data,
+                               C.byref(h)))
+    n = math.prod(int(d) for d in dims)
+    op = Operator(ctx, h, (n, n), dt)
+    op.grid_info = dict(shape=tuple(int(d) for d in dims), taps=t.copy(), has_potential=v is not None,
+                        bytes_per_row=dt.itemsize * (3 if v is not None else 2))
+    return op
+
+
+def host_grid_matrix(shape, taps, potential=None, dtype=None):
+    """The matrix that defines `grid_operator(shape, taps, potential)` as a scipy.sparse.csr_matrix (`ks_host_grid_matrix`: the host
+    path, no device): ascending columns, the diagonal entry centre + potential[r] stored even where it is zero."""
+    import scipy.sparse as sp
+
+    lib = _lib.load()
+    dt, dims, t, v = _grid_args(shape, taps, potential, dtype)
+    ext = [int(d) for d in dims] + [1] * (3 - dims.size)
+    ok = all(1 <= e < 2 ** 31 for e in ext) and ext[0] * ext[1] * ext[2] < 2 ** 31 - 1
+    n = ext[0] * ext[1] * ext[2] if ok else 0
+    nx, ny, nz = ext if ok else (1, 1, 1)
+    nnz = n + 2 * ((nx - 1) * ny * nz + nx * (ny - 1) * nz + nx * ny * (nz - 1)) if ok else 0
+    rowptr, colidx, val = np.zeros(n + 1, dtype=np.int64), np.zeros(max(nnz, 1), dtype=np.int32), np.zeros(max(nnz, 1), dtype=dt)
+    got = C.c_int64()
+    check(lib.ks_host_grid_matrix(int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data, None if v is None else v.ctypes.data,
+                                  rowptr.ctypes.data, colidx.ctypes.data, val.ctypes.data, nnz, C.byref(got)))
+    assert got.value == nnz == rowptr[-1]
+    return sp.csr_matrix((val[:nnz], colidx[:nnz], rowptr), shape=(n, n))
+
+
 def host_operator(fn, n: int, dtype=np.float64, ctx: Context | None = None) -> Operator:
     """Opaque host operator: `fn(y, x)` fills y = A*x on numpy views (a LinearMap wrapping ldiv!,
     docs/src/index.md:246-249).  Columns are staged over PCIe by the library."""

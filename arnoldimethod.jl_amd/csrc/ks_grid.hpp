@@ -1,0 +1,302 @@
+// Matrix-free grid operator  y = A x  for a constant-coefficient 3-, 5- or 7-point stencil plus a per-point diagonal term on an
+// nx x ny x nz grid (ks_operator_grid, include/kschur.h): mul!(y, A, x), src/expansion.jl:121, for A = -Laplacian + V(x) and its
+// kin, with NOTHING stored per non-zero.  The grid shape gives the boundary rows by index arithmetic, the seven taps travel in the
+// kernel arguments, the only per-row datum is the diagonal entry centre + potential[r] (formed once on the host at upload, by the
+// code that ks_host_grid_matrix runs).
+// Part of the ONE translation unit of libkschur_hip.so: included by ks_hip.hip after ks_tridiag.hpp.
+//
+// The operator IS the matrix ks_host_grid_matrix returns: the kernel rounds every product on its own and adds the products of a row
+// to +0.0 in ascending column order (-z, -y, -x, centre, +x, +y, +z; a tap whose neighbour lies outside the grid is skipped), so y
+// carries the bits every stored layout of that matrix gives.
+//
+// k_grid.  A workgroup of 256 threads owns an in-plane tile of TX x TY points (four points per thread) and walks up a range of
+// z-planes.  Per plane every thread keeps its own points of the planes z - 1, z, z + 1 in registers (the +-z taps never touch
+// memory a second time) and the planes z + 2 in flight; the points of plane z go into an LDS tile together with the tile's halo
+// (one cell per thread, loaded two planes ahead), from which the +-x and +-y taps are read.  Two LDS tiles alternate: one barrier
+// per plane.  The z-loop is unrolled by four so that the four register sets rotate by name: nothing waits for a load before the
+// step that uses it.  Compulsory traffic: x read once, the diagonal read once, y written once -- 24 bytes per row in Float64 (16 without
+// a potential), twice that in ComplexF64; on top of it the halo of a tile (2 (TX + TY) / (TX TY) of x: 12.5 % for 32 x 32) and
+// the two planes a z-range reads beyond its own, which neighbouring workgroups of the same XCD bring into its L2.
+// Every access is one element wide (8 bytes in Float64): a row starts at r = nx (...), for odd nx not 16-byte aligned, and nothing
+// here depends on it.
+// Tiles: 32 x 32 for grids with ny > 1, 1024 x 1 for ny == 1 (1-D grids, and nx x 1 x nz).  Work items are (z-range, tile), z-range
+// major, dealt to the XCDs in contiguous runs (xcd_remap) so that neighbouring tiles meet in one L2.
+#pragma once
+
+namespace ksd {
+
+constexpr int kGridMinZ = 8;       // planes per z-range, at least: a range reads two planes beyond its own
+constexpr int kGridWant = 1024;    // work items per launch, at most, while z can be split: what an MI355X holds at once (4 per CU)
+
+template <class T> struct GridDev {
+  int nx = 1, ny = 1, nz = 1;
+  int ntx = 1, nty = 1;   // tiles along x and y
+  int zc = 1;             // planes per z-range
+  T tap[7] = {};          // -z, -y, -x, centre, +x, +y, +z
+};
+
+// shifted: bit 0 -- y = sigma (A x - theta x), the Newton step of the s-step expansion (as k_spmv_stencil2 stores it), bit 1 --
+// cacheable instead of streaming stores.  diag == nullptr: no potential, the diagonal entry is tap[3].
+template <class T, int TX, int TY>
+__global__ void __launch_bounds__(kBlock)
+    k_grid(const GridDev<T> g, const T* __restrict__ x, const T* __restrict__ diag, T* __restrict__ y, const DevState* __restrict__ st,
+           int shifted, T theta, double sigma) {
+  if (st && st->breakdown >= 0) return;
+  constexpr int PPT = TX * TY / kBlock;          // points per thread
+  constexpr int HY = TY > 1 ? 1 : 0;             // halo rows in y (a one-row tile belongs to a grid with ny == 1: no y neighbours)
+  constexpr int LW = TX + 2, LH = TY + 2 * HY;   // LDS tile with its halo
+  constexpr int NHALO = 2 * TY + 2 * HY * TX;    // halo cells (corners are never read)
+  static_assert(TX * TY % kBlock == 0 && NHALO <= kBlock, "four points and at most one halo cell per thread");
+  __shared__ T tile[2][LH * LW];
+  const int ntiles = g.ntx * g.nty;
+  const int item = xcd_remap((int)blockIdx.x, (int)gridDim.x);
+  const int zr = item / ntiles, t2 = item - zr * ntiles;
+  const int tyi = t2 / g.ntx, txi = t2 - tyi * g.ntx;
+  const int x0 = txi * TX, y0 = tyi * TY;
+  const int za = zr * g.zc, zb = min(g.nz, za + g.zc);
+  const int64_t P = (int64_t)g.nx * g.ny;
+  const int tid = (int)threadIdx.x;
+
+  int64_t off[PPT];   // in-plane offset of the owned points
+  int li[PPT];        // ... and their place in the LDS tile
+  bool in[PPT], hxm[PPT], hxp[PPT], hym[PPT], hyp[PPT];   // inside the grid; has a -x / +x / -y / +y neighbour
+#pragma unroll
+  for (int k = 0; k < PPT; ++k) {
+    const int p = tid + k * kBlock;
+    const int lx = p % TX, ly = p / TX;
+    const int gx = x0 + lx, gy = y0 + ly;
+    in[k] = gx < g.nx && gy < g.ny;
+    off[k] = (int64_t)gy * g.nx + gx;
+    li[k] = (ly + HY) * LW + lx + 1;
+    hxm[k] = in[k] && gx > 0;
+    hxp[k] = in[k] && gx + 1 < g.nx;
+    hym[k] = in[k] && gy > 0;
+    hyp[k] = in[k] && gy + 1 < g.ny;
+  }
+  // this thread's halo cell: left column, right column, row below, row above
+  bool hin = false;
+  int64_t hoff = 0;
+  int hli = 0;
+  if (tid < NHALO) {
+    int hx, hy;
+    if (tid < TY) { hx = -1; hy = tid; }
+    else if (tid < 2 * TY) { hx = TX; hy = tid - TY; }
+    else if (tid < 2 * TY + TX) { hx = tid - 2 * TY; hy = -1; }
+    else { hx = tid - 2 * TY - TX; hy = TY; }
+    const int gx = x0 + hx, gy = y0 + hy;
+    hin = gx >= 0 && gx < g.nx && gy >= 0 && gy < g.ny;
+    hoff = (int64_t)gy * g.nx + gx;
+    hli = (hy + HY) * LW + hx + 1;
+  }
+  // (a point outside the grid or the planes is never loaded: zero stands in and is never multiplied into a stored row)
+  auto ldx = [&](int z, int64_t o, bool ok) { return ok && z >= 0 && z < g.nz ? x[(int64_t)z * P + o] : zero_of(T{}); };
+  auto ldd = [&](int z, int64_t o, bool ok) { return ok && z < g.nz ? ld_val(diag + ((int64_t)z * P + o), true) : zero_of(T{}); };
+
+  // Register sets: xr[0..3] hold the owned points of four consecutive planes and rotate by NAME, not by moves (the z-loop is
+  // unrolled by four): a load issued in one step lands in the set that step no longer needs and is first read one barrier and
+  // one step later.  hr[0..1]: this thread's halo cell of the planes of even / odd steps, dr[0..1]: the diagonal likewise.
+  T xr[4][PPT], dr[2][PPT], hr[2];
+  hr[0] = ldx(za, hoff, hin);
+  hr[1] = ldx(za + 1, hoff, hin && za + 1 < zb);
+#pragma unroll
+  for (int k = 0; k < PPT; ++k) {
+    xr[0][k] = ldx(za - 1, off[k], in[k]);
+    xr[1][k] = ldx(za, off[k], in[k]);
+    xr[2][k] = ldx(za + 1, off[k], in[k]);
+    dr[0][k] = diag ? ldd(za, off[k], in[k]) : g.tap[3];
+    dr[1][k] = dr[0][k];
+  }
+  const bool plain_st = (shifted & 2) != 0;
+  // one plane: xm / xc / xp = planes z - 1 / z / z + 1, xn receives plane z + 2; hw = the halo cell of plane z, then of z + 2
+  auto step = [&](int z, const T (&xm)[PPT], const T (&xc)[PPT], const T (&xp)[PPT], T (&xn)[PPT], T& hw, const T (&dc)[PPT], T (&dn)[PPT],
+                  T* __restrict__ tl) {
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) tl[li[k]] = xc[k];
+    if (tid < NHALO) tl[hli] = hw;
+    hw = ldx(z + 2, hoff, hin && z + 2 < zb);
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+      xn[k] = ldx(z + 2, off[k], in[k] && z + 2 <= zb);   // (plane zb is the +z tap of the range's last plane)
+      if (diag) dn[k] = ldd(z + 1, off[k], in[k] && z + 1 < zb);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+      T s = zero_of(T{});
+      if (z > 0) s = add_(s, mul_nc(g.tap[0], xm[k]));
+      if constexpr (HY) {
+        if (hym[k]) s = add_(s, mul_nc(g.tap[1], tl[li[k] - LW]));
+      }
+      if (hxm[k]) s = add_(s, mul_nc(g.tap[2], tl[li[k] - 1]));
+      s = add_(s, mul_nc(dc[k], xc[k]));
+      if (hxp[k]) s = add_(s, mul_nc(g.tap[4], tl[li[k] + 1]));
+      if constexpr (HY) {
+        if (hyp[k]) s = add_(s, mul_nc(g.tap[5], tl[li[k] + LW]));
+      }
+      if (z + 1 < g.nz) s = add_(s, mul_nc(g.tap[6], xp[k]));
+      if (shifted & 1) s = scl(sub_s(s, mul_(theta, xc[k])), sigma);
+      if (in[k]) {
+        T* dst = y + ((int64_t)z * P + off[k]);
+        if (plain_st) *dst = s;
+        else st_elem_nt(dst, s);
+      }
+    }
+  };
+  // (the exits are uniform over the workgroup: the barriers match)
+  for (int z = za; z < zb; z += 4) {
+    step(z, xr[0], xr[1], xr[2], xr[3], hr[0], dr[0], dr[1], tile[0]);
+    if (z + 1 >= zb) break;
+    step(z + 1, xr[1], xr[2], xr[3], xr[0], hr[1], dr[1], dr[0], tile[1]);
+    if (z + 2 >= zb) break;
+    step(z + 2, xr[2], xr[3], xr[0], xr[1], hr[0], dr[0], dr[1], tile[0]);
+    if (z + 3 >= zb) break;
+    step(z + 3, xr[3], xr[0], xr[1], xr[2], hr[1], dr[1], dr[0], tile[1]);
+  }
+}
+
+}  // namespace ksd
+
+namespace {
+namespace grid {
+
+template <class H> inline bool finite_(const H& v) {
+  if constexpr (std::is_same<H, double>::value) return std::isfinite(v);
+  else return std::isfinite(v.real()) && std::isfinite(v.imag());
+}
+// centre + potential[r]: one addition, rounded once (componentwise for ComplexF64)
+inline double diag_add(double c, double v) { return c + v; }
+inline cplx diag_add(cplx c, cplx v) { return cplx(c.real() + v.real(), c.imag() + v.imag()); }
+
+struct Shape {
+  int64_t nx = 1, ny = 1, nz = 1, n = 0, nnz = 0;
+};
+
+// the checks both entry points make (include/kschur.h); `who` starts the message
+template <class H>
+Shape check(const std::string& who, int ndim, const int64_t* dims, const void* taps_v, const void* pot_v) {
+  KS_REQUIRE(ndim >= 1 && ndim <= 3, KS_ERR_ARGUMENT, who + ": ndim = " + std::to_string(ndim) + " (1, 2 or 3 are supported)");
+  KS_REQUIRE(dims && taps_v, KS_ERR_ARGUMENT, who + ": null dims or taps");
+  Shape s;
+  int64_t* ext[3] = {&s.nx, &s.ny, &s.nz};
+  constexpr int64_t kMax = 2147483646;   // rows and columns are 32-bit, like those of every stored matrix
+  int64_t n = 1;
+  for (int a = 0; a < ndim; ++a) {
+    KS_REQUIRE(dims[a] >= 1, KS_ERR_ARGUMENT, who + ": extent " + std::to_string(a) + " is " + std::to_string(dims[a]) + " (must be at least 1)");
+    KS_REQUIRE(dims[a] <= kMax / n, KS_ERR_ARGUMENT,
+               who + ": the grid has more than " + std::to_string(kMax) + " points: n and the plane stride must fit the 32-bit row index");
+    *ext[a] = dims[a];
+    n *= dims[a];
+  }
+  s.n = n;
+  s.nnz = n + 2 * ((s.nx - 1) * s.ny * s.nz + s.nx * (s.ny - 1) * s.nz + s.nx * s.ny * (s.nz - 1));
+  const H* t = static_cast<const H*>(taps_v);
+  for (int k = 0; k < 2 * ndim + 1; ++k)
+    KS_REQUIRE(finite_(t[k]), KS_ERR_ARGUMENT, who + ": tap " + std::to_string(k) + " is not finite");
+  if (pot_v) {
+    const H* v = static_cast<const H*>(pot_v);
+    for (int64_t r = 0; r < n; ++r)
+      KS_REQUIRE(finite_(v[r]), KS_ERR_ARGUMENT, who + ": potential entry " + std::to_string(r) + " is not finite");
+  }
+  return s;
+}
+
+// the 2 ndim + 1 taps in the seven slots -z, -y, -x, centre, +x, +y, +z (slots of a missing dimension: zero, never used)
+template <class H> void seven_taps(int ndim, const H* t, H (&out)[7]) {
+  for (H& o : out) o = H(0);
+  for (int k = 0; k < 2 * ndim + 1; ++k) out[3 - ndim + k] = t[k];
+}
+
+// The matrix the operator is defined by, as 0-based CSR with ascending columns.  rowptr is always filled; colidx / val only when
+// cap >= nnz.
+template <class H>
+void host_matrix(const Shape& s, int ndim, const H* taps, const H* pot, int64_t* rowptr, int32_t* colidx, H* val, int64_t cap, int64_t* nnz) {
+  if (nnz) *nnz = s.nnz;
+  KS_REQUIRE(cap >= s.nnz, KS_ERR_ARGUMENT,
+             "ks_host_grid_matrix: cap = " + std::to_string(cap) + " is too small, the matrix has " + std::to_string(s.nnz) + " entries");
+  KS_REQUIRE(rowptr && (s.nnz == 0 || (colidx && val)), KS_ERR_ARGUMENT, "ks_host_grid_matrix: null output array");
+  H t[7];
+  seven_taps(ndim, taps, t);
+  const int64_t P = s.nx * s.ny;
+  int64_t q = 0, r = 0;
+  for (int64_t iz = 0; iz < s.nz; ++iz)
+    for (int64_t iy = 0; iy < s.ny; ++iy)
+      for (int64_t ix = 0; ix < s.nx; ++ix, ++r) {
+        rowptr[r] = q;
+        auto put = [&](int64_t c, const H& v) { colidx[q] = (int32_t)c; val[q] = v; ++q; };
+        if (iz > 0) put(r - P, t[0]);
+        if (iy > 0) put(r - s.nx, t[1]);
+        if (ix > 0) put(r - 1, t[2]);
+        put(r, pot ? diag_add(t[3], pot[r]) : t[3]);
+        if (ix + 1 < s.nx) put(r + 1, t[4]);
+        if (iy + 1 < s.ny) put(r + s.nx, t[5]);
+        if (iz + 1 < s.nz) put(r + P, t[6]);
+      }
+  rowptr[s.n] = q;
+}
+
+}  // namespace grid
+
+template <class D> struct GridOp : ks_operator {
+  ksd::GridDev<D> g{};
+  D* diag = nullptr;   // centre + potential[r] (null: no potential)
+  int nitems = 0;      // workgroups of a launch
+  bool wide = false;   // the 1024 x 1 tile (ny == 1)
+  double bytes = 0.0;  // algorithmic bytes of one product
+  ~GridOp() override { (void)hipFree(diag); }
+  void launch(const void* xv, void* yv, const DevState* st, int shifted, D theta, double sigma) {
+    KS_REQUIRE(xv != yv, KS_ERR_ARGUMENT, "grid operator: the product needs distinct x and y");
+    ProfScope ps(ctx, KSP_SPMV, bytes);
+    const D* x = static_cast<const D*>(xv);
+    D* y = static_cast<D*>(yv);
+    if (wide) ksd::k_grid<D, 1024, 1><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma);
+    else ksd::k_grid<D, 32, 32><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma);
+    KS_HIP(hipGetLastError());
+  }
+  void apply(const void* x, void* y, const DevState* st) override { launch(x, y, st, 0, D{}, 1.0); }
+  // the Newton step in the same launch (KS_SHIFT_FUSED=0: the product and a streaming pass, like the stored layouts)
+  void apply_shifted(const void* x, void* y, double tre, double tim, double sigma, int64_t ld, const DevState* st) override {
+    if (!env_int("KS_SHIFT_FUSED", 1)) { ks_operator::apply_shifted(x, y, tre, tim, sigma, ld, st); return; }
+    static const int env = env_int("KS_SHIFT_PLAIN", -1);
+    const bool plain = env >= 0 ? env != 0 : shift_store_cacheable;
+    D theta;
+    if constexpr (sizeof(D) == 8) theta = tre; else theta = D{tre, tim};
+    launch(x, y, st, 1 | (plain ? 2 : 0), theta, sigma);
+  }
+};
+
+template <class D>
+ks_operator* make_grid(ks_ctx* ctx, int ndim, const int64_t* dims, const void* taps, const void* potential) {
+  using H = typename HostT<D>::type;
+  const grid::Shape s = grid::check<H>("ks_operator_grid", ndim, dims, taps, potential);
+  auto op = std::make_unique<GridOp<D>>();
+  op->ctx = ctx;
+  op->n_local = s.n;
+  op->nnz = s.nnz;
+  op->dtype = sizeof(D) == 8 ? KS_F64 : KS_C64;
+  H t[7];
+  grid::seven_taps(ndim, static_cast<const H*>(taps), t);
+  static_assert(sizeof(H) == sizeof(D), "element layout");
+  std::memcpy(op->g.tap, t, sizeof(t));
+  op->g.nx = (int)s.nx; op->g.ny = (int)s.ny; op->g.nz = (int)s.nz;
+  op->wide = s.ny == 1;
+  const int64_t tx = op->wide ? 1024 : 32, ty = op->wide ? 1 : 32;
+  op->g.ntx = (int)((s.nx + tx - 1) / tx);
+  op->g.nty = (int)((s.ny + ty - 1) / ty);
+  const int64_t tiles = (int64_t)op->g.ntx * op->g.nty;
+  const int64_t ranges = std::max<int64_t>(1, ksd::kGridWant / tiles);
+  op->g.zc = (int)std::max<int64_t>(ksd::kGridMinZ, (s.nz + ranges - 1) / ranges);
+  const int64_t items = tiles * ((s.nz + op->g.zc - 1) / op->g.zc);
+  KS_REQUIRE(items < (int64_t)2147483647, KS_ERR_ARGUMENT, "ks_operator_grid: too many tiles for one launch");
+  op->nitems = (int)items;
+  if (potential) {
+    const H* v = static_cast<const H*>(potential);
+    std::vector<H> d((size_t)s.n);
+    for (int64_t r = 0; r < s.n; ++r) d[r] = grid::diag_add(t[3], v[r]);
+    KS_HIP(hipMalloc(&op->diag, (size_t)s.n * sizeof(D)));
+    KS_HIP(hipMemcpy(op->diag, d.data(), (size_t)s.n * sizeof(D), hipMemcpyHostToDevice));
+  }
+  op->bytes = (double)s.n * sizeof(D) * (potential ? 3.0 : 2.0);
+  return op.release();
+}
+
+}  // namespace

@@ -41,6 +41,7 @@ using ksd::kBlock;
 #include "ks_sptrsv.hpp"     // shift-invert operator from triangular factors (sparse triangular solves)
 #include "ks_tridiag.hpp"    // tridiagonal shift-invert operator: factored once on the host (ks_tridiag_plan.hpp), applied in HBM
 #include "ks_product.hpp"    // product of operators: generalized problems composed in HBM
+#include "ks_grid.hpp"       // matrix-free grid operator: stencil taps in the kernel arguments plus a per-point diagonal
 #include "ks_workspace.hpp"  // ks_workspace, launch helpers, expansion, rotations
 #include "ks_block.hpp"      // s-step (block) expansion: launchers, shifts, block sizes
 #include "ks_backend.hpp"    // HipBackend, residual checks, placement search
@@ -505,6 +506,16 @@ int ks_operator_product(ks_ctx* ctx, int nops, ks_operator* const* ops, ks_opera
     KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, "ks_operator_product: single-GPU contexts only (the intermediate vectors are not sharded)");
     ctx->use();
     *out = make_product(ctx, nops, ops);
+  });
+}
+
+int ks_operator_grid(ks_ctx* ctx, int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential, ks_operator** out) {
+  return guarded([&] {
+    KS_REQUIRE(ctx && out, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
+    KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, "ks_operator_grid: single-GPU contexts only (the grid is not partitioned across ranks)");
+    ctx->use();
+    *out = dtype == KS_F64 ? make_grid<double>(ctx, ndim, dims, taps, potential) : make_grid<cd>(ctx, ndim, dims, taps, potential);
   });
 }
 
@@ -1649,6 +1660,20 @@ int ks_host_csr_plan(int64_t nrows_local, int64_t ncols, int64_t nnz, const void
       }
       for (int b = 0; cb_bounds && b < (int)P.cb_bounds.size() && b < cb_cap; ++b) cb_bounds[b] = P.cb_bounds[b];
     });
+  });
+}
+
+int ks_host_grid_matrix(int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential, int64_t* rowptr, int32_t* colidx,
+                        void* val, int64_t cap, int64_t* nnz) {
+  return guarded([&] {
+    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
+    if (dtype == KS_F64) {
+      const grid::Shape s = grid::check<double>("ks_host_grid_matrix", ndim, dims, taps, potential);
+      grid::host_matrix<double>(s, ndim, static_cast<const double*>(taps), static_cast<const double*>(potential), rowptr, colidx, static_cast<double*>(val), cap, nnz);
+    } else {
+      const grid::Shape s = grid::check<cplx>("ks_host_grid_matrix", ndim, dims, taps, potential);
+      grid::host_matrix<cplx>(s, ndim, static_cast<const cplx*>(taps), static_cast<const cplx*>(potential), rowptr, colidx, static_cast<cplx*>(val), cap, nnz);
+    }
   });
 }
 

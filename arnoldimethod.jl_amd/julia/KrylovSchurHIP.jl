@@ -46,7 +46,7 @@ using LinearAlgebra, SparseArrays, Random
 import ArnoldiMethod
 import ArnoldiMethod: ArnoldiWorkspace, PartialSchur
 
-export HipContext, HipOperator, HipTridiagonalSolve, HipTridiagonalPencil, HipProduct, tridiag_info, HipWorkspace, HipBasis, HipColumn, HipColumns, hip_partialschur, hip_partialschur!, hip_partialeigen, set_sstep!, relation_breaks
+export HipContext, HipOperator, HipTridiagonalSolve, HipTridiagonalPencil, HipProduct, HipGridOperator, tridiag_info, HipWorkspace, HipBasis, HipColumn, HipColumns, hip_partialschur, hip_partialschur!, hip_partialeigen, set_sstep!, relation_breaks
 
 const LIB = get(ENV, "KSCHUR_LIB", joinpath(@__DIR__, "..", "libkschur_hip.so"))
 
@@ -256,6 +256,28 @@ function HipProduct(ops::HipOperator...)
         check(ccall((:ks_operator_product, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}), ctx.h, Cint(length(ops)), pointer(hs), r))
     end
     _finish_operator(T, r[], ops[1].n, ctx, ops)
+end
+
+# Matrix-free GRID operator: mul!(y, A, x) (src/expansion.jl:121) for a constant-coefficient 3-, 5- or 7-point stencil plus a per-point
+# diagonal term -- A = -Laplacian + V(x) and its kin -- with nothing stored per non-zero (ks_operator_grid): `dims` = (nx,), (nx, ny)
+# or (nx, ny, nz), x fastest, so an `Array` V of size `dims` has the row order in `vec(V)`; `taps`: 2 ndim + 1 values in ascending
+# column order ([-z, -y, -x, centre, +x, +y, +z] in 3-D); a tap whose neighbour lies outside the grid is absent.  The products have
+# the bits of the stored matrix with the same entries.
+function HipGridOperator(ctx::HipContext, dims::NTuple{N,Integer}, taps::AbstractVector; potential::Union{Nothing,AbstractArray} = nothing) where {N}
+    1 <= N <= 3 || throw(ArgumentError("a grid has 1, 2 or 3 dimensions"))
+    T = (eltype(taps) <: Complex || (potential !== nothing && eltype(potential) <: Complex)) ? ComplexF64 : Float64
+    length(taps) == 2N + 1 || throw(DimensionMismatch("a $(N)-D grid takes $(2N + 1) taps"))
+    n = prod(Int64.(dims))
+    (potential === nothing || length(potential) == n) || throw(DimensionMismatch("potential must have $(n) entries"))
+    d = Int64[dims...]; t = Vector{T}(taps)
+    v = potential === nothing ? T[] : Vector{T}(vec(potential))
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve d t v begin
+        check(ccall((:ks_operator_grid, LIB), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{Int64}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),
+                    ctx.h, Cint(N), pointer(d), dtype_code(T), pointer(t), potential === nothing ? C_NULL : pointer(v), r))
+    end
+    _finish_operator(T, r[], n, ctx, nothing)
 end
 
 "Device layout the library chose for a stored matrix: (bytes streamed per non-zero, dictionary size, layout code)."

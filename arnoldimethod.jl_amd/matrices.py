@@ -78,6 +78,16 @@ def _stencil_rows(dims, r0, r1, diag, index_dtype=np.int32):
     return indptr, cand[mask].astype(index_dtype), vals[mask].astype(np.float64)
 
 
+def harmonic_potential(shape, strength: float = 8.0) -> np.ndarray:
+    """V = strength * |(p - centre) / extent|^2 on the points of a grid of `shape` = (nx[, ny[, nz]]), flat in row order (x fastest):
+    the potential of `grid_operator(shape, taps, potential)` in tools/grid_bench.py -- between 0 and strength * ndim / 4."""
+    ax = [((np.arange(m, dtype=np.float64) - (m - 1) / 2.0) / m) ** 2 for m in shape]
+    v = np.zeros(tuple(int(m) for m in shape[::-1]))
+    for a, q in enumerate(ax):
+        v = v + q.reshape([-1 if b == a else 1 for b in range(len(shape))][::-1])
+    return (strength * v).ravel()
+
+
 def laplace3d_eigs(mx: int, my: int, mz: int, k: int | None = None):
     ex = 2 - 2 * np.cos(np.arange(1, mx + 1) * np.pi / (mx + 1))
     ey = 2 - 2 * np.cos(np.arange(1, my + 1) * np.pi / (my + 1))

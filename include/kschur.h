@@ -211,6 +211,30 @@ int ks_operator_tridiag_pencil(ks_ctx* ctx, int64_t n, int dtype, const void* dl
  * error of a factor (a callback returning non-zero) comes out of the call that applied the product, unchanged.  The product is
  * enqueued ahead only if every factor can be; ks_operator_size reports the sum of the factors' nnz, ks_operator_format layout -1. */
 int ks_operator_product(ks_ctx* ctx, int nops, ks_operator* const* ops, ks_operator** out);
+/* (viii) matrix-free grid operator: a constant-coefficient 3-, 5- or 7-point stencil plus a per-point diagonal term (a potential
+ * -Laplacian + V(x), a reaction or mass term) -- mul!(y, A, x), src/expansion.jl:121, with nothing stored per non-zero: the grid
+ * shape gives the boundary rows by index arithmetic, the taps travel in the kernel arguments, the only per-row datum is the
+ * diagonal entry.  A product moves x, the diagonal and y once: 24 bytes per row in Float64 (16 without a potential), twice that
+ * in ComplexF64.  DEFINITION -- the operator is the matrix ks_host_grid_matrix returns:
+ *   grid        nx x ny x nz points, x fastest: row r = ix + nx (iy + ny iz), n = nx ny nz; dims holds ndim extents
+ *               (nx[, ny[, nz]]), for ndim 1 or 2 the missing extents are 1
+ *   taps        2 ndim + 1 values of `dtype` in ascending column order: [-z, -y, -x, centre, +x, +y, +z] in 3-D,
+ *               [-y, -x, centre, +x, +y] in 2-D, [-x, centre, +x] in 1-D
+ *   boundaries  a tap whose neighbour lies outside the grid is absent (Dirichlet truncation, no wrap-around: the last point of
+ *               an x-line and the first of the next are not neighbours)
+ *   diagonal    entry of row r: centre + potential[r] -- one addition, rounded once, componentwise for ComplexF64 -- stored even
+ *               when the sum is zero; potential == NULL: centre
+ *   product     every product is rounded on its own and added to +0.0 in ascending column order: y has the bits every stored
+ *               layout gives, i.e. the product is bit-identical to ks_operator_csr applied to the matrix of
+ *               ks_host_grid_matrix, and a whole solve is interchangeable between the two
+ * KS_ERR_ARGUMENT (the message names the cause): ndim outside 1...3, an extent < 1, more than 2^31 - 2 points (n and the plane
+ * stride must fit the 32-bit row index of the stored matrix), a non-finite tap or potential entry, a multi-rank context.
+ * ks_operator_size reports n and the number of in-grid taps, ks_operator_format 0 / 0 / -1.  The operator is enqueued ahead like a
+ * stored matrix; products are deterministic; x is never written, rows >= n of y are never written; x and y of a product must be
+ * distinct.  The Newton step of the s-step expansion is one launch of the same kernel (KS_SHIFT_FUSED=0: the product and a pass). */
+int ks_operator_grid(ks_ctx* ctx, int ndim, const int64_t* dims /* ndim entries: nx[, ny[, nz]] */, int dtype,
+                     const void* taps /* 2*ndim+1 values of dtype */, const void* potential /* n values of dtype, or NULL */,
+                     ks_operator** out);
 int ks_operator_destroy(ks_operator* op);
 int ks_operator_size(const ks_operator* op, int64_t* n_local, int64_t* nnz, int* dtype);
 /* Device layout chosen for a stored matrix at upload (mul!(y, A, x), src/expansion.jl:121; all layouts give bit-identical y):
@@ -579,6 +603,12 @@ int ks_host_csr_plan(int64_t nrows_local, int64_t ncols, int64_t nnz, const void
                      int64_t nghost, int64_t nlow, int* plan_layout, int* ndict, double* bytes_per_nnz,
                      double* aux_bytes, int64_t* facts, int32_t* stencil_delta, int64_t* blkrow, int64_t* blkptr,
                      int64_t blk_cap, int64_t* cb_bounds, int cb_cap);
+/* The matrix that DEFINES ks_operator_grid (mul!(y, A, x), src/expansion.jl:121), as 0-based CSR with ascending columns, without
+ * a device: rowptr n + 1 entries, colidx / val `cap` entries.  *nnz (may be NULL) receives the number of stored entries -- the
+ * in-grid taps, n + 2 ((nx-1) ny nz + nx (ny-1) nz + nx ny (nz-1)) -- also when the call fails because cap is smaller than that
+ * (KS_ERR_ARGUMENT; nothing else is written then).  Same refusals as the operator, except that no context is involved. */
+int ks_host_grid_matrix(int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential,
+                        int64_t* rowptr /* n+1 */, int32_t* colidx, void* val, int64_t cap, int64_t* nnz);
 /* The plan, the factors and the HOST apply of ks_operator_tridiag_solve without a device (docs/src/index.md:234-259: the
  * factorize / ldiv! pair of the shift-invert recipe): x[:, k] = (T - sigma I)^-1 b[:, k] for nrhs columns (column k at b + k ldb,
  * x + k ldx; b and x distinct), walking exactly the arrays the device kernels read, in their order.  Same refusals as the operator. */

@@ -1,0 +1,163 @@
+#!/usr/bin/env python3
+"""The matrix-free grid operator (ks_operator_grid) against the stored layouts, in the solver's own access pattern:
+
+    python tools/grid_bench.py [--sizes 216,100] [--rounds 7] [--chains 5] [--cycles 20] [--no-solve]
+
+Float64, 7-point -Laplacian (+ a harmonic potential) on m x m x m grids.  Per size, in ONE process:
+
+  products   the chain column i -> column i + 1 over the 41 columns of a 20/40 workspace (a basis that does not fit the caches),
+             `chains` chains per round, every timed region closed by a device synchronisation; the operators alternate inside
+             every round, so a difference is seen against the spread of the same session (a host clock: at 100^3 it measures the
+             enqueue, not the kernel -- the HIP-event time of the kernels alone is printed next to it):
+               (a) grid_operator with a potential              24 n bytes
+               (b) csr_operator(host_grid_matrix(...))         the same matrix stored: the only way to run it without (a)
+               (c) grid_operator without a potential           16 n bytes
+               (d) csr_operator of the plain Laplacian         the stencil layout (marching kernel)
+  solve      iterations/s of nev = 20, mindim / maxdim = 20 / 40, :SR on (a) and (b): `cycles` timed restart cycles after 3 warm-up
+             cycles (what bench.py times), alternating (a) and (b) per round.
+
+Prints one JSON line per size and a short table; fractions are of the 8 TB/s HBM rate."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+sys.path.insert(0, ROOT)
+from __graft_entry__ import import_package  # noqa: E402
+
+ks = import_package()
+PEAK = 8.0e12
+LAPLACE = np.array([-1.0, -1.0, -1.0, 6.0, -1.0, -1.0, -1.0])
+MAXDIM, MINDIM, NEV = 40, 20, 20
+
+
+def stats(v):
+    v = np.asarray(v, dtype=np.float64)
+    return dict(mean=float(v.mean()), std=float(v.std(ddof=1)) if v.size > 1 else 0.0, min=float(v.min()), max=float(v.max()),
+                rounds=[round(float(x), 3) for x in v])
+
+
+def bench_products(ctx, ops, n, rounds, chains):
+    ws = ks.ArnoldiWorkspace(n, MAXDIM, np.float64, ctx=ctx)
+    ws.fill_uniform(0, 1)
+    us = {name: [] for name in ops}
+    for name, op in ops.items():      # warm-up: every operator over every column
+        for i in range(MAXDIM):
+            ws.apply(op, i, i + 1)
+    ctx.synchronize()
+    for _ in range(rounds):
+        for name, op in ops.items():
+            ws.fill_uniform(0, 1)     # (keeps the chain's values in range; untimed)
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            for _c in range(chains):
+                for i in range(MAXDIM):
+                    ws.apply(op, i, i + 1)
+            ctx.synchronize()
+            us[name].append(1e6 * (time.perf_counter() - t0) / (chains * MAXDIM))
+    out = {name: stats(v) for name, v in us.items()}
+    # the kernels alone: the library's HIP-event profile (class "spmv"), in a pass of its own -- the events slow the enqueue down
+    ctx.profile_enable(True)
+    for name, op in ops.items():
+        ctx.profile_reset()
+        for _c in range(chains):
+            for i in range(MAXDIM):
+                ws.apply(op, i, i + 1)
+        ctx.synchronize()
+        p = ctx.profile_get()["spmv"]
+        out[name]["event_us"] = 1e3 * p["ms"] / max(p["count"], 1)
+        out[name]["event_launches_per_product"] = p["count"] / (chains * MAXDIM)
+    ctx.profile_enable(False)
+    ws.close()
+    return out
+
+
+class Solve:
+    """bench.py's cycle: expand_restart from the basis size the previous restart left, synchronised."""
+
+    def __init__(self, ctx, op, n):
+        self.ctx, self.op = ctx, op
+        self.ws = ks.ArnoldiWorkspace(n, MAXDIM, np.float64, ctx=ctx)
+        self.ws.reinitialize(0, ks.matrices.start_vector(n))
+        self.ws.iterate_arnoldi(op, 1, MINDIM)
+        self.k, self.active, self.trail = MINDIM, 0, []
+
+    def cycles(self, count):
+        tol = float(np.sqrt(np.finfo(np.float64).eps))
+        self.ctx.synchronize()
+        steps, t0 = 0, time.perf_counter()
+        for _ in range(count):
+            r = self.ws.expand_restart(self.op, self.k, self.active, NEV, "SR", tol, MINDIM, MAXDIM)
+            self.ctx.synchronize()
+            steps += MAXDIM - self.k
+            self.k, self.active = r["k"], r["nlock"]
+            self.trail.append((self.k, self.active))
+        return steps / (time.perf_counter() - t0)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="216,100")
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--chains", type=int, default=5)
+    ap.add_argument("--cycles", type=int, default=20)
+    ap.add_argument("--no-solve", action="store_true")
+    args = ap.parse_args()
+    ctx = ks.Context(0)
+    for m in (int(s) for s in args.sizes.split(",")):
+        shape, n = (m, m, m), m ** 3
+        V = ks.matrices.harmonic_potential(shape)
+        t0 = time.perf_counter()
+        A = ks.host_grid_matrix(shape, LAPLACE, V)
+        ip, ix, dv = ks.matrices.laplace3d_csr(m, m, m)
+        ops = {
+            "a_grid_potential": ks.grid_operator(shape, LAPLACE, V, ctx=ctx),
+            "b_stored_potential": ks.csr_operator(A, ctx),
+            "c_grid_plain": ks.grid_operator(shape, LAPLACE, ctx=ctx),
+            "d_stored_laplacian": ks.csr_operator(ks.matrices.to_scipy(ip, ix, dv, n), ctx),
+        }
+        setup_s = time.perf_counter() - t0
+        nnz = A.nnz
+        del A, ip, ix, dv
+        fmt = {k: ops[k].format for k in ("b_stored_potential", "d_stored_laplacian")}
+        by = {"a_grid_potential": 24.0 * n, "c_grid_plain": 16.0 * n,
+              "b_stored_potential": fmt["b_stored_potential"]["bytes_per_nnz"] * nnz + 16.0 * n,
+              "d_stored_laplacian": fmt["d_stored_laplacian"]["bytes_per_nnz"] * nnz + 16.0 * n}
+        out = dict(m=m, n=n, nnz=nnz, setup_seconds=round(setup_s, 2), formats=fmt, chains=args.chains, products_per_round=args.chains * MAXDIM)
+        prod = bench_products(ctx, ops, n, args.rounds, args.chains)
+        for name, s in prod.items():
+            s["bytes_per_product"] = by[name]
+            s["hbm_fraction_at_mean"] = by[name] / (s["mean"] * 1e-6) / PEAK
+        out["us_per_product"] = prod
+        if not args.no_solve:
+            runs = {name: Solve(ctx, ops[name], n) for name in ("a_grid_potential", "b_stored_potential")}
+            for s in runs.values():
+                s.cycles(3)
+            rate = {name: [] for name in runs}
+            for _ in range(max(3, args.rounds // 2)):
+                for name, s in runs.items():
+                    rate[name].append(s.cycles(args.cycles))
+            out["iterations_per_s"] = {name: stats(v) for name, v in rate.items()}
+            out["same_restart_trail"] = runs["a_grid_potential"].trail == runs["b_stored_potential"].trail
+            out["blocks"] = {name: s.ws.sstep_info["blocks"] for name, s in runs.items()}
+            for s in runs.values():
+                s.ws.close()
+        print(json.dumps(out), flush=True)
+        print("m = %d (n = %d): us per product, mean +- std [min, max] over %d rounds of %d products; fraction of 8 TB/s" % (m, n, args.rounds, args.chains * MAXDIM))
+        for name, s in prod.items():
+            print("  %-20s %8.2f +- %5.2f  [%7.2f, %7.2f]   %5.1f B/row  %5.1f %%   kernels alone (HIP events) %7.2f us" % (
+                name, s["mean"], s["std"], s["min"], s["max"], s["bytes_per_product"] / n, 100 * s["hbm_fraction_at_mean"], s["event_us"]))
+        if not args.no_solve:
+            for name, s in out["iterations_per_s"].items():
+                print("  %-20s %8.0f +- %5.0f iterations/s  [%7.0f, %7.0f]" % (name, s["mean"], s["std"], s["min"], s["max"]))
+        sys.stdout.flush()
+        for op in ops.values():
+            op.close()
+
+
+if __name__ == "__main__":
+    main()
