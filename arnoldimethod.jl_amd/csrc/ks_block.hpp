@@ -88,7 +88,7 @@ template <class D> int launch_blk(ks_workspace* ws, int which, int k, int s, boo
   if (zscratch) { a.zsrc = ws->zscratch; a.ldz = ws->ld; }
   if (which == 2) { a.cin = ws->rot_cin; a.out0 = ws->rot_out0; a.rotm = ws->Qd; }
   a.partial = ws->bpart; a.pnb = ws->pnb; a.coefp = bs->coefp; a.r1inv = bs->r1inv; a.zeros = ws->bzero; a.st = ws->st;
-  a.dbg = blk_dbg(); a.nt = ws->v_nt ? 1 : 0; a.num_cu = ws->ctx->num_cu; a.bpc = ws->ctx->bpc; a.stream = ws->ctx->stream;
+  a.dbg = blk_dbg(); a.nt = ws->v_nt ? 1 : 0; a.num_cu = ws->ctx->num_cu; a.bpc = ws->ctx->bpc; a.grid_cap = ws->grid_cap; a.stream = ws->ctx->stream;
   try {
     return ks_blk_launch(which, a);
   } catch (const std::runtime_error& e) {

@@ -34,7 +34,8 @@ template <class K> int resident(const BlkLaunchArgs& a, K kernel, int& cache, in
 inline int cap(const BlkLaunchArgs& a, int nb, int packs_per_iter, size_t esz) {
   const int64_t npacks = a.ld * (int64_t)esz / 16;
   const int64_t want = std::max<int64_t>(1, npacks / (2 * (int64_t)packs_per_iter));
-  return (int)std::min<int64_t>(nb, want);
+  const int g = (int)std::min<int64_t>(nb, want);
+  return a.grid_cap > 0 ? std::min(g, a.grid_cap) : g;
 }
 
 // ring form of pass 1 (Float64 wide instantiations; KS_BLK_RING=0: the register form)

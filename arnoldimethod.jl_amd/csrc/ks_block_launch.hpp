@@ -20,6 +20,7 @@ struct BlkLaunchArgs {
   int dbg;             // probe flags (1: second pass without stores)
   int nt;              // non-temporal loads of the basis
   int num_cu, bpc;     // device CUs, cap on resident workgroups per CU (ks_ctx::bpc)
+  int grid_cap = 0;    // upper bound on the workgroups of a launch, 0 = none (ks_workspace::grid_cap)
   hipStream_t stream;
   // block columns read from elsewhere than V[:, k : k + s) (matrix-instruction forms of both passes and the fused
   // rotation: the Newton chain was written to scratch columns); null: in place

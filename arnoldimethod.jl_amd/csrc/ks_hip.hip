@@ -618,6 +618,9 @@ int ks_workspace_create(ks_ctx* ctx, int64_t n_local, int64_t n_global, int64_t 
     w->pstride = (int)round_up(maxdim + 2, 8);
     w->esz = dtype == KS_F64 ? 8 : 16;
     w->pnb = ctx->nblocks();
+    w->grid_cap = std::max(0, env_int("KS_GRID_CAP", 0));
+    w->fused_wb = env_int("KS_FUSED_WB", 0);
+    w->fused_wb_min_mb = env_int("KS_FUSED_WB_MIN_MB", 24);
     w->nb = cap_blocks(w.get(), w->pnb, 2 * kBlock);  // generic streaming grid
     const size_t esz = w->esz;
     const size_t vbytes = (size_t)w->ld * (maxdim + 1) * esz;

@@ -202,6 +202,10 @@ struct ks_workspace {
   int gate_cin = 0, gate_rmax = 0;     // shape the armed rotation was launched for
   int nb = 0;               // streaming workgroups (capped for small problems)
   int pnb = 0;              // column stride of `partial` (>= every producer's grid)
+  // read once at creation: KS_GRID_CAP (0 = off: upper bound on the workgroups of every row-streaming launch -- runs the
+  // many-trips-per-workgroup forms of the kernels at small sizes), KS_FUSED_WB / KS_FUSED_WB_MIN_MB (launch_axpy_dots)
+  int grid_cap = 0;
+  int fused_wb = 0, fused_wb_min_mb = 24;
   uint64_t seed = 20240917ull;
   uint64_t rng_count = 0;
 
@@ -253,10 +257,12 @@ namespace {
 
 inline void gate_cancel(ks_workspace* ws);  // (reverse mailbox, below: nothing may synchronise the stream behind an armed gate)
 
+// KS_GRID_CAP only ever LOWERS a grid (the partial-sum buffers sized by pnb stay large enough)
+inline int cap_grid(const ks_workspace* ws, int nb) { return ws->grid_cap > 0 ? std::min(nb, ws->grid_cap) : nb; }
 inline int cap_blocks(const ks_workspace* ws, int nb, int packs_per_iter) {
   const int64_t npacks = ws->ld * (int64_t)ws->esz / 16;
   const int64_t want = std::max<int64_t>(1, npacks / (2 * (int64_t)packs_per_iter));
-  return (int)std::min<int64_t>(nb, want);
+  return cap_grid(ws, (int)std::min<int64_t>(nb, want));
 }
 
 uint64_t next_seed(ks_workspace* ws) {
@@ -399,8 +405,7 @@ template <class D> int launch_axpy_dots(ks_workspace* ws, int j, D* w, int defer
   KS_REQUIRE(j >= 1 && j <= kFusedMaxJ, KS_ERR_INTERNAL, "fused projection kernel covers 1 <= j <= 64");
   // (one workgroup per CU is too little parallelism while the basis is cache resident: 8 MiB columns lose 3 % with the deep
   // staging, 80 MiB columns gain 11 % -- deep staging from KS_FUSED_WB_MIN_MB (24) MiB per column on)
-  static const int wb_env = env_int("KS_FUSED_WB", 0);
-  static const int wb_min_mb = env_int("KS_FUSED_WB_MIN_MB", 24);
+  const int wb_env = ws->fused_wb, wb_min_mb = ws->fused_wb_min_mb;  // (KS_FUSED_WB / KS_FUSED_WB_MIN_MB at creation)
   const bool wb_small = wb_env ? wb_env <= 8 : (ws->ld * (int64_t)sizeof(D) < ((int64_t)wb_min_mb << 20));
   if (wb_small) {
     switch ((j + 3) / 4) {
@@ -928,7 +933,7 @@ void gemm_tall_chunked(ks_workspace* ws, const TV* V, int c, int r, const TY* Yd
   for (int r0 = 0; r0 < r; r0 += rc_max) {
     const int rc = std::min(rc_max, r - r0);
     const size_t smem = (size_t)c * rc * sizeof(TY);
-    ksd::k_gemm_tall<TV, TY><<<ctx->num_cu * 4, kBlock, smem, ctx->stream>>>(V, ws->ld, ws->n, c, rc, Yd + (size_t)r0 * ldy, ldy,
+    ksd::k_gemm_tall<TV, TY><<<cap_grid(ws, ctx->num_cu * 4), kBlock, smem, ctx->stream>>>(V, ws->ld, ws->n, c, rc, Yd + (size_t)r0 * ldy, ldy,
                                                                           out + (size_t)r0 * ldo, ldo);
   }
   KS_HIP(hipGetLastError());
@@ -986,7 +991,7 @@ template <class D> void rotate_device(ks_workspace* ws, int c0, int c, int r, in
       auto smem = [&](int KC) { return (size_t)ntile * 16 * (4 * KC + 1) * 8; };
       static const int rt = env_int("KS_ROTATE_RT", 2);
       static const int nbm = env_int("KS_ROTATE_BPC", 4);
-      const int nbr = ctx->num_cu * nbm;
+      const int nbr = cap_grid(ws, ctx->num_cu * nbm);
       if (c <= 24) { if (rt == 2) ksd::k_rotate_mfma<6, 2><<<nbr, kBlock, smem(6), s>>>(Vc, ws->ld, c, r, Qd, c, out0, extra_out); else ksd::k_rotate_mfma<6, 1><<<nbr, kBlock, smem(6), s>>>(Vc, ws->ld, c, r, Qd, c, out0, extra_out); }
       else if (c <= 40) { if (rt == 2) ksd::k_rotate_mfma<10, 2><<<nbr, kBlock, smem(10), s>>>(Vc, ws->ld, c, r, Qd, c, out0, extra_out); else ksd::k_rotate_mfma<10, 1><<<nbr, kBlock, smem(10), s>>>(Vc, ws->ld, c, r, Qd, c, out0, extra_out); }
       else if (c <= 44) { if (rt == 2) ksd::k_rotate_mfma<11, 2><<<nbr, kBlock, smem(11), s>>>(Vc, ws->ld, c, r, Qd, c, out0, extra_out); else ksd::k_rotate_mfma<11, 1><<<nbr, kBlock, smem(11), s>>>(Vc, ws->ld, c, r, Qd, c, out0, extra_out); }
@@ -996,7 +1001,7 @@ template <class D> void rotate_device(ks_workspace* ws, int c0, int c, int r, in
     }
   }
   const size_t smem = (size_t)c * r * sizeof(D);
-  const int nb = ctx->num_cu * 2;
+  const int nb = cap_grid(ws, ctx->num_cu * 2);
   D* Vo = Vc + (size_t)out0 * ws->ld;
   const int xo = extra_out >= 0 ? extra_out - out0 : -1;  // relative to the output base
   if (c <= 8) ksd::k_rotate_valu<D, 8><<<nb, kBlock, smem, s>>>(Vc, ws->ld, c, r, Qd, c, Vo, ws->ld, xo);
