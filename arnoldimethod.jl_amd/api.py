@@ -504,7 +504,40 @@ def _grid_args(shape, taps, potential, dtype):
     return dt, np.ascontiguousarray(dims), t, v
 
 
-def grid_operator(shape, taps, potential=None, dtype=None, ctx: Context | None = None) -> Operator:
+def _grid_wrap_args(dims, t, v, dt, dtype, periodic, wrap):
+    """(dtype, taps, potential, flags, wrap or None) of a grid operator with periodic axes: `periodic` a bool or one bool per axis,
+    `wrap` 2 ndim values in the order of the taps without the centre.  A complex `wrap` promotes the element type like complex taps
+    do; a pinned Float64 refuses an imaginary part."""
+    ndim = int(dims.size)
+    if periodic is None:
+        periodic = False
+    if isinstance(periodic, (bool, np.bool_)):
+        flags = np.full(ndim, int(bool(periodic)), dtype=np.int32)
+    else:
+        try:
+            seq = list(periodic)
+        except TypeError as e:
+            raise ArgumentError(f"periodic must be a bool or a sequence of {ndim} bools: {periodic!r}") from e
+        if len(seq) != ndim or not all(isinstance(p, (bool, np.bool_)) for p in seq):
+            raise DimensionMismatch(f"periodic takes one bool per axis in the order of shape ({ndim}), got {periodic!r}")
+        flags = np.array([int(bool(p)) for p in seq], dtype=np.int32)
+    w = None
+    if wrap is not None:
+        w = np.asarray(wrap)
+        if w.shape != (2 * ndim,):
+            raise DimensionMismatch(f"a {ndim}-D grid takes {2 * ndim} wrap values in the order of the taps without the centre, got shape {w.shape}")
+        if w.dtype.kind == "c" and dt.kind == "f":
+            if dtype is None:   # promote, like complex taps do
+                dt = np.dtype(np.complex128)
+                t = t.astype(dt)
+                v = None if v is None else v.astype(dt)
+            elif np.any(w.imag != 0):
+                raise ArgumentError("wrap has an imaginary part but the element type is Float64 (KS_F64)")
+        w = np.ascontiguousarray(w.real if dt.kind == "f" else w, dtype=dt)
+    return dt, t, v, flags, w
+
+
+def grid_operator(shape, taps, potential=None, dtype=None, ctx: Context | None = None, periodic=None, wrap=None) -> Operator:
     """Matrix-free operator of a constant-coefficient 3-, 5- or 7-point stencil plus a per-point diagonal term on a grid
     (`ks_operator_grid`): mul!(y, A, x), src/expansion.jl:121, for A = -Laplacian + V(x) and its kin with nothing stored per
     non-zero -- 24 bytes per row and product in Float64 (16 without a potential) where a stored matrix with a varying diagonal
@@ -514,23 +547,38 @@ def grid_operator(shape, taps, potential=None, dtype=None, ctx: Context | None =
     column order, [-z, -y, -x, centre, +x, +y, +z] in 3-D; a tap whose neighbour lies outside the grid is absent (no wrap-around).
     `potential`: None, or n values added to the centre tap -- flat in row order, or an array of shape (nz, ny, nx) / (ny, nx) in C
     order (so that `potential.ravel()` is the row order).  The operator is exactly the matrix `host_grid_matrix` returns, and its
-    products have the bits `csr_operator` of that matrix gives.  `operator.grid_info`: shape, taps, has_potential, bytes_per_row."""
+    products have the bits `csr_operator` of that matrix gives.  `operator.grid_info`: shape, taps, has_potential, bytes_per_row,
+    periodic, wrap.
+
+    `periodic` (`ks_operator_grid_periodic`): True, or one bool per axis in the order of `shape` -- on such an axis (extent >= 3)
+    the first and the last point of a line are neighbours.  `wrap`: 2 ndim values in the order of the taps without the centre
+    ([-z, -y, -x, +x, +y, +z] in 3-D), the entries of the links that cross the boundary; None = the taps (plain periodicity),
+    `extras.bloch_wrap(taps, theta)` = Bloch phases, `-taps` = antiperiodic.  The traffic per row is unchanged."""
     ctx = ctx or default_context()
     lib = _lib.load()
     dt, dims, t, v = _grid_args(shape, taps, potential, dtype)
     h = C.c_void_p()
-    check(lib.ks_operator_grid(ctx._h, int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data, None if v is None else v.ctypes.data,
-                               C.byref(h)))
+    flags, w = np.zeros(dims.size, dtype=np.int32), None
+    if periodic is None and wrap is None:
+        check(lib.ks_operator_grid(ctx._h, int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data, None if v is None else v.ctypes.data,
+                                   C.byref(h)))
+    else:
+        dt, t, v, flags, w = _grid_wrap_args(dims, t, v, dt, dtype, periodic, wrap)
+        check(lib.ks_operator_grid_periodic(ctx._h, int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data,
+                                            None if v is None else v.ctypes.data, flags.ctypes.data, None if w is None else w.ctypes.data,
+                                            C.byref(h)))
     n = math.prod(int(d) for d in dims)
     op = Operator(ctx, h, (n, n), dt)
     op.grid_info = dict(shape=tuple(int(d) for d in dims), taps=t.copy(), has_potential=v is not None,
-                        bytes_per_row=dt.itemsize * (3 if v is not None else 2))
+                        bytes_per_row=dt.itemsize * (3 if v is not None else 2), periodic=tuple(bool(f) for f in flags),
+                        wrap=None if w is None else w.copy())
     return op
 
 
-def host_grid_matrix(shape, taps, potential=None, dtype=None):
+def host_grid_matrix(shape, taps, potential=None, dtype=None, periodic=None, wrap=None):
     """The matrix that defines `grid_operator(shape, taps, potential)` as a scipy.sparse.csr_matrix (`ks_host_grid_matrix`: the host
-    path, no device): ascending columns, the diagonal entry centre + potential[r] stored even where it is zero."""
+    path, no device): ascending columns, the diagonal entry centre + potential[r] stored even where it is zero.  `periodic`, `wrap`:
+    as for `grid_operator` (`ks_host_grid_matrix_periodic`)."""
     import scipy.sparse as sp
 
     lib = _lib.load()
@@ -540,10 +588,18 @@ def host_grid_matrix(shape, taps, potential=None, dtype=None):
     n = ext[0] * ext[1] * ext[2] if ok else 0
     nx, ny, nz = ext if ok else (1, 1, 1)
     nnz = n + 2 * ((nx - 1) * ny * nz + nx * (ny - 1) * nz + nx * ny * (nz - 1)) if ok else 0
-    rowptr, colidx, val = np.zeros(n + 1, dtype=np.int64), np.zeros(max(nnz, 1), dtype=np.int32), np.zeros(max(nnz, 1), dtype=dt)
     got = C.c_int64()
-    check(lib.ks_host_grid_matrix(int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data, None if v is None else v.ctypes.data,
-                                  rowptr.ctypes.data, colidx.ctypes.data, val.ctypes.data, nnz, C.byref(got)))
+    if periodic is None and wrap is None:
+        rowptr, colidx, val = np.zeros(n + 1, dtype=np.int64), np.zeros(max(nnz, 1), dtype=np.int32), np.zeros(max(nnz, 1), dtype=dt)
+        check(lib.ks_host_grid_matrix(int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data, None if v is None else v.ctypes.data,
+                                      rowptr.ctypes.data, colidx.ctypes.data, val.ctypes.data, nnz, C.byref(got)))
+    else:
+        dt, t, v, flags, w = _grid_wrap_args(dims, t, v, dt, dtype, periodic, wrap)
+        nnz += sum(2 * (n // e) for e, f in zip(ext, flags) if f) if ok else 0   # (an extent < 3: the library's refusal to make)
+        rowptr, colidx, val = np.zeros(n + 1, dtype=np.int64), np.zeros(max(nnz, 1), dtype=np.int32), np.zeros(max(nnz, 1), dtype=dt)
+        check(lib.ks_host_grid_matrix_periodic(int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data,
+                                               None if v is None else v.ctypes.data, flags.ctypes.data, None if w is None else w.ctypes.data,
+                                               rowptr.ctypes.data, colidx.ctypes.data, val.ctypes.data, nnz, C.byref(got)))
     assert got.value == nnz == rowptr[-1]
     return sp.csr_matrix((val[:nnz], colidx[:nnz], rowptr), shape=(n, n))
 

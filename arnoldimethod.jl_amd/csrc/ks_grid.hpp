@@ -34,14 +34,28 @@ template <class T> struct GridDev {
   int zc = 1;             // planes per z-range
   T tap[7] = {};          // -z, -y, -x, centre, +x, +y, +z
 };
+// ... with periodic axes (ks_operator_grid_periodic): the entries of the links that cross the cell boundary and the axes that wrap.
+// A type of its own, so that the open operator's kernel and its arguments are what they were.
+template <class T> struct GridPerDev : GridDev<T> {
+  T wrap[6] = {};         // -z, -y, -x, +x, +y, +z
+  int px = 0, py = 0, pz = 0;
+};
 
 // shifted: bit 0 -- y = sigma (A x - theta x), the Newton step of the s-step expansion (as k_spmv_stencil2 stores it), bit 1 --
 // cacheable instead of streaming stores.  diag == nullptr: no potential, the diagonal entry is tap[3].
-template <class T, int TX, int TY>
+//
+// G = GridPerDev<T>: periodic axes.  A row is summed in the 13-slot order of include/kschur.h (ix), a wrap link at ANOTHER place than
+// the interior link of its direction: the column of a +wrap link lies below every other column of its axis, that of a -wrap link
+// above.  x and y: a halo cell one step outside the grid loads from the other end of its line.  When the last tile is partial the
+// +x neighbour of gx = nx - 1 is no halo cell but the LDS slot of the OWNED point gx = nx, which then holds x[0] of the line
+// (ldk, loff; likewise gy = ny); such a point is still never stored, and no row without that neighbour reads it.  z: plane -1 is
+// plane nz - 1, plane nz is plane 0 (only the first and the last z-range meet them).
+template <class T, int TX, int TY, class G>
 __global__ void __launch_bounds__(kBlock)
-    k_grid(const GridDev<T> g, const T* __restrict__ x, const T* __restrict__ diag, T* __restrict__ y, const DevState* __restrict__ st,
+    k_grid(const G g, const T* __restrict__ x, const T* __restrict__ diag, T* __restrict__ y, const DevState* __restrict__ st,
            int shifted, T theta, double sigma) {
   if (st && st->breakdown >= 0) return;
+  constexpr bool PER = !std::is_same<G, GridDev<T>>::value;
   constexpr int PPT = TX * TY / kBlock;          // points per thread
   constexpr int HY = TY > 1 ? 1 : 0;             // halo rows in y (a one-row tile belongs to a grid with ny == 1: no y neighbours)
   constexpr int LW = TX + 2, LH = TY + 2 * HY;   // LDS tile with its halo
@@ -60,6 +74,9 @@ __global__ void __launch_bounds__(kBlock)
   int64_t off[PPT];   // in-plane offset of the owned points
   int li[PPT];        // ... and their place in the LDS tile
   bool in[PPT], hxm[PPT], hxp[PPT], hym[PPT], hyp[PPT];   // inside the grid; has a -x / +x / -y / +y neighbour
+  // periodic: the point is loaded (in the grid, or the wrap image one step beyond it) from loff; its -x / +x / -y / +y link wraps
+  bool ldk[PPT], wxm[PPT], wxp[PPT], wym[PPT], wyp[PPT];
+  int64_t loff[PPT];
 #pragma unroll
   for (int k = 0; k < PPT; ++k) {
     const int p = tid + k * kBlock;
@@ -72,6 +89,15 @@ __global__ void __launch_bounds__(kBlock)
     hxp[k] = in[k] && gx + 1 < g.nx;
     hym[k] = in[k] && gy > 0;
     hyp[k] = in[k] && gy + 1 < g.ny;
+    if constexpr (PER) {
+      wxm[k] = in[k] && g.px && gx == 0;
+      wxp[k] = in[k] && g.px && gx + 1 == g.nx;
+      wym[k] = in[k] && g.py && gy == 0;
+      wyp[k] = in[k] && g.py && gy + 1 == g.ny;
+      const bool ix = g.px && gx == g.nx && gy < g.ny, iy = g.py && gy == g.ny && gx < g.nx;   // the image of x[0, gy] / of x[gx, 0]
+      ldk[k] = in[k] || ix || iy;
+      loff[k] = ix ? (int64_t)gy * g.nx : iy ? (int64_t)gx : off[k];
+    }
   }
   // this thread's halo cell: left column, right column, row below, row above
   bool hin = false;
@@ -83,13 +109,27 @@ __global__ void __launch_bounds__(kBlock)
     else if (tid < 2 * TY) { hx = TX; hy = tid - TY; }
     else if (tid < 2 * TY + TX) { hx = tid - 2 * TY; hy = -1; }
     else { hx = tid - 2 * TY - TX; hy = TY; }
-    const int gx = x0 + hx, gy = y0 + hy;
+    int gx = x0 + hx, gy = y0 + hy;
+    if constexpr (PER) {
+      if (g.px) gx = gx == -1 ? g.nx - 1 : gx == g.nx ? 0 : gx;
+      if (g.py) gy = gy == -1 ? g.ny - 1 : gy == g.ny ? 0 : gy;
+    }
     hin = gx >= 0 && gx < g.nx && gy >= 0 && gy < g.ny;
     hoff = (int64_t)gy * g.nx + gx;
     hli = (hy + HY) * LW + hx + 1;
   }
   // (a point outside the grid or the planes is never loaded: zero stands in and is never multiplied into a stored row)
-  auto ldx = [&](int z, int64_t o, bool ok) { return ok && z >= 0 && z < g.nz ? x[(int64_t)z * P + o] : zero_of(T{}); };
+  auto ldx = [&](int z, int64_t o, bool ok) {
+    if constexpr (PER) {
+      if (g.pz) z = z < 0 ? g.nz - 1 : z >= g.nz ? 0 : z;   // (z is never further out than one plane)
+    }
+    return ok && z >= 0 && z < g.nz ? x[(int64_t)z * P + o] : zero_of(T{});
+  };
+  // the owned points as they are LOADED: with periodic axes also the wrap images beyond a partial last tile
+  auto ldo = [&](int z, int k, bool ok) {
+    if constexpr (PER) return ldx(z, loff[k], ldk[k] && ok);
+    else return ldx(z, off[k], in[k] && ok);
+  };
   auto ldd = [&](int z, int64_t o, bool ok) { return ok && z < g.nz ? ld_val(diag + ((int64_t)z * P + o), true) : zero_of(T{}); };
 
   // Register sets: xr[0..3] hold the owned points of four consecutive planes and rotate by NAME, not by moves (the z-loop is
@@ -100,9 +140,9 @@ __global__ void __launch_bounds__(kBlock)
   hr[1] = ldx(za + 1, hoff, hin && za + 1 < zb);
 #pragma unroll
   for (int k = 0; k < PPT; ++k) {
-    xr[0][k] = ldx(za - 1, off[k], in[k]);
-    xr[1][k] = ldx(za, off[k], in[k]);
-    xr[2][k] = ldx(za + 1, off[k], in[k]);
+    xr[0][k] = ldo(za - 1, k, true);
+    xr[1][k] = ldo(za, k, true);
+    xr[2][k] = ldo(za + 1, k, true);
     dr[0][k] = diag ? ldd(za, off[k], in[k]) : g.tap[3];
     dr[1][k] = dr[0][k];
   }
@@ -116,24 +156,42 @@ __global__ void __launch_bounds__(kBlock)
     hw = ldx(z + 2, hoff, hin && z + 2 < zb);
 #pragma unroll
     for (int k = 0; k < PPT; ++k) {
-      xn[k] = ldx(z + 2, off[k], in[k] && z + 2 <= zb);   // (plane zb is the +z tap of the range's last plane)
+      xn[k] = ldo(z + 2, k, z + 2 <= zb);   // (plane zb is the +z tap of the range's last plane)
       if (diag) dn[k] = ldd(z + 1, off[k], in[k] && z + 1 < zb);
     }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < PPT; ++k) {
       T s = zero_of(T{});
+      if constexpr (PER) {
+        if (g.pz && z + 1 == g.nz) s = add_(s, mul_nc(g.wrap[5], xp[k]));
+      }
       if (z > 0) s = add_(s, mul_nc(g.tap[0], xm[k]));
       if constexpr (HY) {
+        if constexpr (PER) {
+          if (wyp[k]) s = add_(s, mul_nc(g.wrap[4], tl[li[k] + LW]));
+        }
         if (hym[k]) s = add_(s, mul_nc(g.tap[1], tl[li[k] - LW]));
+      }
+      if constexpr (PER) {
+        if (wxp[k]) s = add_(s, mul_nc(g.wrap[3], tl[li[k] + 1]));
       }
       if (hxm[k]) s = add_(s, mul_nc(g.tap[2], tl[li[k] - 1]));
       s = add_(s, mul_nc(dc[k], xc[k]));
       if (hxp[k]) s = add_(s, mul_nc(g.tap[4], tl[li[k] + 1]));
+      if constexpr (PER) {
+        if (wxm[k]) s = add_(s, mul_nc(g.wrap[2], tl[li[k] - 1]));
+      }
       if constexpr (HY) {
         if (hyp[k]) s = add_(s, mul_nc(g.tap[5], tl[li[k] + LW]));
+        if constexpr (PER) {
+          if (wym[k]) s = add_(s, mul_nc(g.wrap[1], tl[li[k] - LW]));
+        }
       }
       if (z + 1 < g.nz) s = add_(s, mul_nc(g.tap[6], xp[k]));
+      if constexpr (PER) {
+        if (g.pz && z == 0) s = add_(s, mul_nc(g.wrap[0], xm[k]));
+      }
       if (shifted & 1) s = scl(sub_s(s, mul_(theta, xc[k])), sigma);
       if (in[k]) {
         T* dst = y + ((int64_t)z * P + off[k]);
@@ -200,6 +258,39 @@ Shape check(const std::string& who, int ndim, const int64_t* dims, const void* t
   return s;
 }
 
+// The periodic axes and the entries of their boundary-crossing links (ks_host_grid_matrix_periodic, include/kschur.h): flags in the
+// order of dims, wrap = 2 ndim values in the order of the taps without the centre, null = the taps themselves.
+template <class H> struct Wrap {
+  bool per[3] = {false, false, false};   // x, y, z
+  H w[6] = {};                           // -z, -y, -x, +x, +y, +z (an axis that does not wrap: zero, never used)
+  bool any() const { return per[0] || per[1] || per[2]; }
+};
+template <class H>
+Wrap<H> check_wrap(const std::string& who, Shape& s, int ndim, const void* taps_v, const int* periodic, const void* wrap_v) {
+  Wrap<H> W;
+  if (!periodic) return W;
+  static const char* const axis[3] = {"x", "y", "z"};
+  const int64_t ext[3] = {s.nx, s.ny, s.nz};
+  const H* t = static_cast<const H*>(taps_v);
+  const H* w = static_cast<const H*>(wrap_v);
+  for (int a = 0; a < ndim; ++a) {
+    if (!periodic[a]) continue;
+    KS_REQUIRE(ext[a] >= 3, KS_ERR_ARGUMENT,
+               who + ": periodic axis " + std::to_string(a) + " (" + axis[a] + ") has extent " + std::to_string(ext[a]) +
+                   " (a periodic axis needs at least 3 points: at 2 the two neighbours coincide, at 1 the link is a self-link)");
+    W.per[a] = true;
+    // axis a: its - link is entry ndim - 1 - a of wrap (entry ndim - 1 - a of the taps), its + link entry ndim + a (tap ndim + 1 + a)
+    const int km = ndim - 1 - a, kp = ndim + a;
+    const H vm = w ? w[km] : t[km], vp = w ? w[kp] : t[kp + 1];
+    KS_REQUIRE(finite_(vm), KS_ERR_ARGUMENT, who + ": wrap value " + std::to_string(km) + " (-" + axis[a] + ") is not finite");
+    KS_REQUIRE(finite_(vp), KS_ERR_ARGUMENT, who + ": wrap value " + std::to_string(kp) + " (+" + axis[a] + ") is not finite");
+    W.w[2 - a] = vm;
+    W.w[3 + a] = vp;
+    s.nnz += 2 * (s.n / ext[a]);   // the two links per line that truncation leaves out
+  }
+  return W;
+}
+
 // the 2 ndim + 1 taps in the seven slots -z, -y, -x, centre, +x, +y, +z (slots of a missing dimension: zero, never used)
 template <class H> void seven_taps(int ndim, const H* t, H (&out)[7]) {
   for (H& o : out) o = H(0);
@@ -207,13 +298,15 @@ template <class H> void seven_taps(int ndim, const H* t, H (&out)[7]) {
 }
 
 // The matrix the operator is defined by, as 0-based CSR with ascending columns.  rowptr is always filled; colidx / val only when
-// cap >= nnz.
+// cap >= nnz.  With periodic axes a row is a sub-sequence of the 13 slots of include/kschur.h (ix): the link of the last point of a
+// line to the first has the lowest column of its axis, that of the first to the last the highest.
 template <class H>
-void host_matrix(const Shape& s, int ndim, const H* taps, const H* pot, int64_t* rowptr, int32_t* colidx, H* val, int64_t cap, int64_t* nnz) {
+void host_matrix(const std::string& who, const Shape& s, int ndim, const H* taps, const H* pot, const Wrap<H>& W, int64_t* rowptr,
+                 int32_t* colidx, H* val, int64_t cap, int64_t* nnz) {
   if (nnz) *nnz = s.nnz;
   KS_REQUIRE(cap >= s.nnz, KS_ERR_ARGUMENT,
-             "ks_host_grid_matrix: cap = " + std::to_string(cap) + " is too small, the matrix has " + std::to_string(s.nnz) + " entries");
-  KS_REQUIRE(rowptr && (s.nnz == 0 || (colidx && val)), KS_ERR_ARGUMENT, "ks_host_grid_matrix: null output array");
+             who + ": cap = " + std::to_string(cap) + " is too small, the matrix has " + std::to_string(s.nnz) + " entries");
+  KS_REQUIRE(rowptr && (s.nnz == 0 || (colidx && val)), KS_ERR_ARGUMENT, who + ": null output array");
   H t[7];
   seven_taps(ndim, taps, t);
   const int64_t P = s.nx * s.ny;
@@ -223,21 +316,37 @@ void host_matrix(const Shape& s, int ndim, const H* taps, const H* pot, int64_t*
       for (int64_t ix = 0; ix < s.nx; ++ix, ++r) {
         rowptr[r] = q;
         auto put = [&](int64_t c, const H& v) { colidx[q] = (int32_t)c; val[q] = v; ++q; };
+        if (W.per[2] && iz + 1 == s.nz) put(r - (s.nz - 1) * P, W.w[5]);
         if (iz > 0) put(r - P, t[0]);
+        if (W.per[1] && iy + 1 == s.ny) put(r - (s.ny - 1) * s.nx, W.w[4]);
         if (iy > 0) put(r - s.nx, t[1]);
+        if (W.per[0] && ix + 1 == s.nx) put(r - (s.nx - 1), W.w[3]);
         if (ix > 0) put(r - 1, t[2]);
         put(r, pot ? diag_add(t[3], pot[r]) : t[3]);
         if (ix + 1 < s.nx) put(r + 1, t[4]);
+        if (W.per[0] && ix == 0) put(r + (s.nx - 1), W.w[2]);
         if (iy + 1 < s.ny) put(r + s.nx, t[5]);
+        if (W.per[1] && iy == 0) put(r + (s.ny - 1) * s.nx, W.w[1]);
         if (iz + 1 < s.nz) put(r + P, t[6]);
+        if (W.per[2] && iz == 0) put(r + (s.nz - 1) * P, W.w[0]);
       }
   rowptr[s.n] = q;
+}
+
+// both host entry points: the checks, then the matrix
+template <class H>
+void host_matrix_entry(const std::string& who, int ndim, const int64_t* dims, const void* taps, const void* pot, const int* periodic,
+                       const void* wrap, int64_t* rowptr, int32_t* colidx, void* val, int64_t cap, int64_t* nnz) {
+  Shape s = check<H>(who, ndim, dims, taps, pot);
+  const Wrap<H> W = check_wrap<H>(who, s, ndim, taps, periodic, wrap);
+  host_matrix<H>(who, s, ndim, static_cast<const H*>(taps), static_cast<const H*>(pot), W, rowptr, colidx, static_cast<H*>(val), cap, nnz);
 }
 
 }  // namespace grid
 
 template <class D> struct GridOp : ks_operator {
-  ksd::GridDev<D> g{};
+  ksd::GridPerDev<D> g{};   // (the open operator's kernel takes its GridDev part)
+  bool periodic = false;  // some axis wraps: the kernel's periodic instantiation
   D* diag = nullptr;   // centre + potential[r] (null: no potential)
   int nitems = 0;      // workgroups of a launch
   bool wide = false;   // the 1024 x 1 tile (ny == 1)
@@ -248,8 +357,12 @@ template <class D> struct GridOp : ks_operator {
     ProfScope ps(ctx, KSP_SPMV, bytes);
     const D* x = static_cast<const D*>(xv);
     D* y = static_cast<D*>(yv);
-    if (wide) ksd::k_grid<D, 1024, 1><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma);
-    else ksd::k_grid<D, 32, 32><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma);
+    const ksd::GridDev<D>& go = g;
+    if (periodic) {
+      if (wide) ksd::k_grid<D, 1024, 1, ksd::GridPerDev<D>><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma);
+      else ksd::k_grid<D, 32, 32, ksd::GridPerDev<D>><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma);
+    } else if (wide) ksd::k_grid<D, 1024, 1, ksd::GridDev<D>><<<nitems, kBlock, 0, ctx->stream>>>(go, x, diag, y, st, shifted, theta, sigma);
+    else ksd::k_grid<D, 32, 32, ksd::GridDev<D>><<<nitems, kBlock, 0, ctx->stream>>>(go, x, diag, y, st, shifted, theta, sigma);
     KS_HIP(hipGetLastError());
   }
   void apply(const void* x, void* y, const DevState* st) override { launch(x, y, st, 0, D{}, 1.0); }
@@ -265,9 +378,11 @@ template <class D> struct GridOp : ks_operator {
 };
 
 template <class D>
-ks_operator* make_grid(ks_ctx* ctx, int ndim, const int64_t* dims, const void* taps, const void* potential) {
+ks_operator* make_grid(ks_ctx* ctx, const std::string& who, int ndim, const int64_t* dims, const void* taps, const void* potential,
+                       const int* periodic, const void* wrap) {
   using H = typename HostT<D>::type;
-  const grid::Shape s = grid::check<H>("ks_operator_grid", ndim, dims, taps, potential);
+  grid::Shape s = grid::check<H>(who, ndim, dims, taps, potential);
+  const grid::Wrap<H> W = grid::check_wrap<H>(who, s, ndim, taps, periodic, wrap);
   auto op = std::make_unique<GridOp<D>>();
   op->ctx = ctx;
   op->n_local = s.n;
@@ -277,6 +392,9 @@ ks_operator* make_grid(ks_ctx* ctx, int ndim, const int64_t* dims, const void* t
   grid::seven_taps(ndim, static_cast<const H*>(taps), t);
   static_assert(sizeof(H) == sizeof(D), "element layout");
   std::memcpy(op->g.tap, t, sizeof(t));
+  std::memcpy(op->g.wrap, W.w, sizeof(W.w));
+  op->g.px = W.per[0]; op->g.py = W.per[1]; op->g.pz = W.per[2];
+  op->periodic = W.any();
   op->g.nx = (int)s.nx; op->g.ny = (int)s.ny; op->g.nz = (int)s.nz;
   op->wide = s.ny == 1;
   const int64_t tx = op->wide ? 1024 : 32, ty = op->wide ? 1 : 32;
@@ -286,7 +404,7 @@ ks_operator* make_grid(ks_ctx* ctx, int ndim, const int64_t* dims, const void* t
   const int64_t ranges = std::max<int64_t>(1, ksd::kGridWant / tiles);
   op->g.zc = (int)std::max<int64_t>(ksd::kGridMinZ, (s.nz + ranges - 1) / ranges);
   const int64_t items = tiles * ((s.nz + op->g.zc - 1) / op->g.zc);
-  KS_REQUIRE(items < (int64_t)2147483647, KS_ERR_ARGUMENT, "ks_operator_grid: too many tiles for one launch");
+  KS_REQUIRE(items < (int64_t)2147483647, KS_ERR_ARGUMENT, who + ": too many tiles for one launch");
   op->nitems = (int)items;
   if (potential) {
     const H* v = static_cast<const H*>(potential);

@@ -515,7 +515,20 @@ int ks_operator_grid(ks_ctx* ctx, int ndim, const int64_t* dims, int dtype, cons
     KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
     KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, "ks_operator_grid: single-GPU contexts only (the grid is not partitioned across ranks)");
     ctx->use();
-    *out = dtype == KS_F64 ? make_grid<double>(ctx, ndim, dims, taps, potential) : make_grid<cd>(ctx, ndim, dims, taps, potential);
+    *out = dtype == KS_F64 ? make_grid<double>(ctx, "ks_operator_grid", ndim, dims, taps, potential, nullptr, nullptr)
+                           : make_grid<cd>(ctx, "ks_operator_grid", ndim, dims, taps, potential, nullptr, nullptr);
+  });
+}
+
+int ks_operator_grid_periodic(ks_ctx* ctx, int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential,
+                              const int* periodic, const void* wrap, ks_operator** out) {
+  return guarded([&] {
+    KS_REQUIRE(ctx && out, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
+    KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, "ks_operator_grid_periodic: single-GPU contexts only (the grid is not partitioned across ranks)");
+    ctx->use();
+    *out = dtype == KS_F64 ? make_grid<double>(ctx, "ks_operator_grid_periodic", ndim, dims, taps, potential, periodic, wrap)
+                           : make_grid<cd>(ctx, "ks_operator_grid_periodic", ndim, dims, taps, potential, periodic, wrap);
   });
 }
 
@@ -1670,13 +1683,17 @@ int ks_host_grid_matrix(int ndim, const int64_t* dims, int dtype, const void* ta
                         void* val, int64_t cap, int64_t* nnz) {
   return guarded([&] {
     KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
-    if (dtype == KS_F64) {
-      const grid::Shape s = grid::check<double>("ks_host_grid_matrix", ndim, dims, taps, potential);
-      grid::host_matrix<double>(s, ndim, static_cast<const double*>(taps), static_cast<const double*>(potential), rowptr, colidx, static_cast<double*>(val), cap, nnz);
-    } else {
-      const grid::Shape s = grid::check<cplx>("ks_host_grid_matrix", ndim, dims, taps, potential);
-      grid::host_matrix<cplx>(s, ndim, static_cast<const cplx*>(taps), static_cast<const cplx*>(potential), rowptr, colidx, static_cast<cplx*>(val), cap, nnz);
-    }
+    if (dtype == KS_F64) grid::host_matrix_entry<double>("ks_host_grid_matrix", ndim, dims, taps, potential, nullptr, nullptr, rowptr, colidx, val, cap, nnz);
+    else grid::host_matrix_entry<cplx>("ks_host_grid_matrix", ndim, dims, taps, potential, nullptr, nullptr, rowptr, colidx, val, cap, nnz);
+  });
+}
+
+int ks_host_grid_matrix_periodic(int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential, const int* periodic,
+                                 const void* wrap, int64_t* rowptr, int32_t* colidx, void* val, int64_t cap, int64_t* nnz) {
+  return guarded([&] {
+    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
+    if (dtype == KS_F64) grid::host_matrix_entry<double>("ks_host_grid_matrix_periodic", ndim, dims, taps, potential, periodic, wrap, rowptr, colidx, val, cap, nnz);
+    else grid::host_matrix_entry<cplx>("ks_host_grid_matrix_periodic", ndim, dims, taps, potential, periodic, wrap, rowptr, colidx, val, cap, nnz);
   });
 }
 

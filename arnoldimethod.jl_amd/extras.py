@@ -199,3 +199,23 @@ def b_orthonormal_operator(A, L, ctx: api.Context | None = None):
     # the same back-transformation on the device: Q = api.schur_vectors(P).apply(back.operator)
     back.operator = op.factors[2]
     return op, back
+
+
+def bloch_wrap(taps, theta) -> np.ndarray:
+    """The `wrap` array of `api.grid_operator(..., periodic=..., wrap=...)` for Bloch boundary conditions: the link that leaves the
+    cell in the + direction of axis a carries t_{+a} e^{+i theta_a}, the one in the - direction t_{-a} e^{-i theta_a} (a band
+    structure at the k-point theta_a = k_a L_a).  `taps`: the 2 ndim + 1 taps in ascending column order; `theta`: one phase per axis
+    in the order of the shape (x[, y[, z]]).  Returns 2 ndim complex values in the order of the taps without the centre.  With
+    symmetric real taps (or t_{-a} = conj(t_{+a})) the operator is Hermitian."""
+    t = np.asarray(taps)
+    th = np.atleast_1d(np.asarray(theta, dtype=np.float64))
+    if t.ndim != 1 or t.size not in (3, 5, 7):
+        raise api.DimensionMismatch(f"taps must hold 3, 5 or 7 values, got shape {t.shape}")
+    ndim = (t.size - 1) // 2
+    if th.shape != (ndim,):
+        raise api.DimensionMismatch(f"theta takes one phase per axis ({ndim}), got shape {th.shape}")
+    w = np.empty(2 * ndim, dtype=np.complex128)
+    for a in range(ndim):
+        w[ndim - 1 - a] = t[ndim - 1 - a] * np.exp(-1j * th[a])
+        w[ndim + a] = t[ndim + 1 + a] * np.exp(1j * th[a])
+    return w

@@ -263,15 +263,33 @@ end
 # or (nx, ny, nz), x fastest, so an `Array` V of size `dims` has the row order in `vec(V)`; `taps`: 2 ndim + 1 values in ascending
 # column order ([-z, -y, -x, centre, +x, +y, +z] in 3-D); a tap whose neighbour lies outside the grid is absent.  The products have
 # the bits of the stored matrix with the same entries.
-function HipGridOperator(ctx::HipContext, dims::NTuple{N,Integer}, taps::AbstractVector; potential::Union{Nothing,AbstractArray} = nothing) where {N}
+# `periodic`: `true`, or one flag per axis in the order of `dims` -- those axes wrap (ks_operator_grid_periodic; an extent of at least 3
+# each).  `wrap`: 2 ndim values in the order of the taps without the centre ([-z, -y, -x, +x, +y, +z] in 3-D), the entries of the links
+# that cross the cell boundary; `nothing` = the taps (plain periodicity), t e^{+-i theta} = Bloch, -taps = antiperiodic.
+function HipGridOperator(ctx::HipContext, dims::NTuple{N,Integer}, taps::AbstractVector; potential::Union{Nothing,AbstractArray} = nothing,
+                         periodic::Union{Nothing,Bool,NTuple{N,Bool},AbstractVector{Bool}} = nothing,
+                         wrap::Union{Nothing,AbstractVector} = nothing) where {N}
     1 <= N <= 3 || throw(ArgumentError("a grid has 1, 2 or 3 dimensions"))
-    T = (eltype(taps) <: Complex || (potential !== nothing && eltype(potential) <: Complex)) ? ComplexF64 : Float64
+    T = (eltype(taps) <: Complex || (potential !== nothing && eltype(potential) <: Complex) || (wrap !== nothing && eltype(wrap) <: Complex)) ? ComplexF64 : Float64
     length(taps) == 2N + 1 || throw(DimensionMismatch("a $(N)-D grid takes $(2N + 1) taps"))
     n = prod(Int64.(dims))
     (potential === nothing || length(potential) == n) || throw(DimensionMismatch("potential must have $(n) entries"))
     d = Int64[dims...]; t = Vector{T}(taps)
     v = potential === nothing ? T[] : Vector{T}(vec(potential))
     r = Ref{Ptr{Cvoid}}(C_NULL)
+    if periodic !== nothing || wrap !== nothing
+        flags = periodic === nothing ? fill(Cint(0), N) : periodic isa Bool ? fill(Cint(periodic), N) : Cint[periodic...]
+        length(flags) == N || throw(DimensionMismatch("periodic takes one flag per axis ($(N))"))
+        (wrap === nothing || length(wrap) == 2N) || throw(DimensionMismatch("a $(N)-D grid takes $(2N) wrap values"))
+        w = wrap === nothing ? T[] : Vector{T}(wrap)
+        GC.@preserve d t v flags w begin
+            check(ccall((:ks_operator_grid_periodic, LIB), Cint,
+                        (Ptr{Cvoid}, Cint, Ptr{Int64}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cint}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),
+                        ctx.h, Cint(N), pointer(d), dtype_code(T), pointer(t), potential === nothing ? C_NULL : pointer(v), pointer(flags),
+                        wrap === nothing ? C_NULL : pointer(w), r))
+        end
+        return _finish_operator(T, r[], n, ctx, nothing)
+    end
     GC.@preserve d t v begin
         check(ccall((:ks_operator_grid, LIB), Cint,
                     (Ptr{Cvoid}, Cint, Ptr{Int64}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),

@@ -235,6 +235,30 @@ int ks_operator_product(ks_ctx* ctx, int nops, ks_operator* const* ops, ks_opera
 int ks_operator_grid(ks_ctx* ctx, int ndim, const int64_t* dims /* ndim entries: nx[, ny[, nz]] */, int dtype,
                      const void* taps /* 2*ndim+1 values of dtype */, const void* potential /* n values of dtype, or NULL */,
                      ks_operator** out);
+/* (ix) ... with periodic axes: crystal Hamiltonians, band structures at a k-point (Bloch phases on the links that cross the cell
+ * boundary), lattice models on a torus -- mul!(y, A, x), src/expansion.jl:121, still with nothing stored per non-zero and the same
+ * compulsory traffic.  Everything of (viii) holds, with these additions.  DEFINITION -- the operator is the matrix
+ * ks_host_grid_matrix_periodic returns:
+ *   periodic    ndim flags in the order of dims (x[, y[, z]]); NULL: no axis wraps.  On a periodic axis of extent m the point at
+ *               index 0 has a - neighbour at index m - 1 and the point at m - 1 a + neighbour at 0; an axis that is not periodic
+ *               is truncated as in (viii)
+ *   wrap        2 ndim values of `dtype` in the order of the taps with the centre left out ([-z, -y, -x, +x, +y, +z] in 3-D): the
+ *               entry of the link that crosses the boundary in that direction.  NULL: the taps themselves (plain periodicity).
+ *               Bloch: wrap[+-x] = t e^{+-i theta_x}; antiperiodic: wrap = -taps.  Values of axes that do not wrap are neither
+ *               read nor checked
+ *   row         columns ascending: a row is a sub-sequence of 13 slots, each present or absent by index arithmetic,
+ *                 +z wrap (iz = nz-1) | -z | +y wrap (iy = ny-1) | -y | +x wrap (ix = nx-1) | -x | centre |
+ *                 +x | -x wrap (ix = 0) | +y | -y wrap (iy = 0) | +z | -z wrap (iz = 0)
+ *               -- a wrap link stands (and is summed) at another place than the interior link of its direction
+ *   product     every product rounded on its own and added to +0.0 in this order: bit-identical to ks_operator_csr of the matrix
+ * KS_ERR_ARGUMENT in addition (the message names the cause and the axis or index): a periodic axis of extent < 3 (at 2 the two
+ * neighbours coincide, at 1 the link is a self-link: the matrix would need duplicate or merged entries), a non-finite wrap value
+ * of a periodic axis.  ks_operator_size reports nnz = n (1 + 2 #periodic axes) + 2 sum over the open axes a of (m_a - 1) n / m_a.
+ * With no periodic axis the operator is that of ks_operator_grid. */
+int ks_operator_grid_periodic(ks_ctx* ctx, int ndim, const int64_t* dims /* ndim entries: nx[, ny[, nz]] */, int dtype,
+                              const void* taps /* 2*ndim+1 values of dtype */, const void* potential /* n values of dtype, or NULL */,
+                              const int* periodic /* ndim flags, or NULL */, const void* wrap /* 2*ndim values of dtype, or NULL */,
+                              ks_operator** out);
 int ks_operator_destroy(ks_operator* op);
 int ks_operator_size(const ks_operator* op, int64_t* n_local, int64_t* nnz, int* dtype);
 /* Device layout chosen for a stored matrix at upload (mul!(y, A, x), src/expansion.jl:121; all layouts give bit-identical y):
@@ -609,6 +633,12 @@ int ks_host_csr_plan(int64_t nrows_local, int64_t ncols, int64_t nnz, const void
  * (KS_ERR_ARGUMENT; nothing else is written then).  Same refusals as the operator, except that no context is involved. */
 int ks_host_grid_matrix(int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential,
                         int64_t* rowptr /* n+1 */, int32_t* colidx, void* val, int64_t cap, int64_t* nnz);
+/* ... and the matrix that DEFINES ks_operator_grid_periodic (mul!(y, A, x), src/expansion.jl:121): `periodic` and `wrap` as there,
+ * every row a sub-sequence of its 13 slots, *nnz = n (1 + 2 #periodic axes) + 2 sum over the open axes a of (m_a - 1) n / m_a.  With
+ * no periodic axis the arrays are those of ks_host_grid_matrix.  Same refusals as that operator, except that no context is involved. */
+int ks_host_grid_matrix_periodic(int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential,
+                                 const int* periodic /* ndim flags, or NULL */, const void* wrap /* 2*ndim values, or NULL */,
+                                 int64_t* rowptr /* n+1 */, int32_t* colidx, void* val, int64_t cap, int64_t* nnz);
 /* The plan, the factors and the HOST apply of ks_operator_tridiag_solve without a device (docs/src/index.md:234-259: the
  * factorize / ldiv! pair of the shift-invert recipe): x[:, k] = (T - sigma I)^-1 b[:, k] for nrhs columns (column k at b + k ldb,
  * x + k ldx; b and x distinct), walking exactly the arrays the device kernels read, in their order.  Same refusals as the operator. */

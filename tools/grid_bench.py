@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The matrix-free grid operator (ks_operator_grid) against the stored layouts, in the solver's own access pattern:
 
-    python tools/grid_bench.py [--sizes 216,100] [--rounds 7] [--chains 5] [--cycles 20] [--no-solve]
+    python tools/grid_bench.py [--sizes 216,100] [--rounds 7] [--chains 5] [--cycles 20] [--no-solve] [--periodic]
 
 Float64, 7-point -Laplacian (+ a harmonic potential) on m x m x m grids.  Per size, in ONE process:
 
@@ -13,8 +13,13 @@ Float64, 7-point -Laplacian (+ a harmonic potential) on m x m x m grids.  Per si
                (b) csr_operator(host_grid_matrix(...))         the same matrix stored: the only way to run it without (a)
                (c) grid_operator without a potential           16 n bytes
                (d) csr_operator of the plain Laplacian         the stencil layout (marching kernel)
+             --periodic adds, on the torus (ks_operator_grid_periodic):
+               (e) grid_operator(..., periodic=True) with the potential     24 n bytes, as (a)
+               (f) csr_operator(host_grid_matrix(..., periodic=True))       the same matrix stored
+             The HIP-event time is taken per round as well (`event_rounds`): its mean and max - min are what two builds are
+             compared by.
   solve      iterations/s of nev = 20, mindim / maxdim = 20 / 40, :SR on (a) and (b): `cycles` timed restart cycles after 3 warm-up
-             cycles (what bench.py times), alternating (a) and (b) per round.
+             cycles (what bench.py times), alternating (a) and (b) -- and (e) and (f) with --periodic -- per round.
 
 Prints one JSON line per size and a short table; fractions are of the 8 TB/s HBM rate."""
 import argparse
@@ -62,15 +67,20 @@ def bench_products(ctx, ops, n, rounds, chains):
     out = {name: stats(v) for name, v in us.items()}
     # the kernels alone: the library's HIP-event profile (class "spmv"), in a pass of its own -- the events slow the enqueue down
     ctx.profile_enable(True)
-    for name, op in ops.items():
-        ctx.profile_reset()
-        for _c in range(chains):
-            for i in range(MAXDIM):
-                ws.apply(op, i, i + 1)
-        ctx.synchronize()
-        p = ctx.profile_get()["spmv"]
-        out[name]["event_us"] = 1e3 * p["ms"] / max(p["count"], 1)
-        out[name]["event_launches_per_product"] = p["count"] / (chains * MAXDIM)
+    ev = {name: [] for name in ops}
+    for _ in range(rounds):
+        for name, op in ops.items():
+            ctx.profile_reset()
+            for _c in range(chains):
+                for i in range(MAXDIM):
+                    ws.apply(op, i, i + 1)
+            ctx.synchronize()
+            p = ctx.profile_get()["spmv"]
+            ev[name].append(1e3 * p["ms"] / max(p["count"], 1))
+            out[name]["event_launches_per_product"] = p["count"] / (chains * MAXDIM)
+    for name, v in ev.items():
+        out[name]["event_rounds"] = stats(v)
+        out[name]["event_us"] = out[name]["event_rounds"]["mean"]
     ctx.profile_enable(False)
     ws.close()
     return out
@@ -106,6 +116,7 @@ def main():
     ap.add_argument("--chains", type=int, default=5)
     ap.add_argument("--cycles", type=int, default=20)
     ap.add_argument("--no-solve", action="store_true")
+    ap.add_argument("--periodic", action="store_true", help="add (e) the periodic grid operator and (f) its stored matrix")
     args = ap.parse_args()
     ctx = ks.Context(0)
     for m in (int(s) for s in args.sizes.split(",")):
@@ -120,21 +131,29 @@ def main():
             "c_grid_plain": ks.grid_operator(shape, LAPLACE, ctx=ctx),
             "d_stored_laplacian": ks.csr_operator(ks.matrices.to_scipy(ip, ix, dv, n), ctx),
         }
+        nnz = {"b_stored_potential": A.nnz, "d_stored_laplacian": A.nnz}
+        if args.periodic:
+            Ap = ks.host_grid_matrix(shape, LAPLACE, V, periodic=True)
+            ops["e_grid_periodic"] = ks.grid_operator(shape, LAPLACE, V, ctx=ctx, periodic=True)
+            ops["f_stored_periodic"] = ks.csr_operator(Ap, ctx)
+            nnz["f_stored_periodic"] = Ap.nnz
+            del Ap
         setup_s = time.perf_counter() - t0
-        nnz = A.nnz
         del A, ip, ix, dv
-        fmt = {k: ops[k].format for k in ("b_stored_potential", "d_stored_laplacian")}
-        by = {"a_grid_potential": 24.0 * n, "c_grid_plain": 16.0 * n,
-              "b_stored_potential": fmt["b_stored_potential"]["bytes_per_nnz"] * nnz + 16.0 * n,
-              "d_stored_laplacian": fmt["d_stored_laplacian"]["bytes_per_nnz"] * nnz + 16.0 * n}
+        fmt = {k: ops[k].format for k in nnz}
+        by = {"a_grid_potential": 24.0 * n, "c_grid_plain": 16.0 * n, "e_grid_periodic": 24.0 * n}
+        by.update({k: fmt[k]["bytes_per_nnz"] * nnz[k] + 16.0 * n for k in nnz})
+        nnz = nnz["b_stored_potential"]
         out = dict(m=m, n=n, nnz=nnz, setup_seconds=round(setup_s, 2), formats=fmt, chains=args.chains, products_per_round=args.chains * MAXDIM)
         prod = bench_products(ctx, ops, n, args.rounds, args.chains)
         for name, s in prod.items():
             s["bytes_per_product"] = by[name]
             s["hbm_fraction_at_mean"] = by[name] / (s["mean"] * 1e-6) / PEAK
+            s["hbm_fraction_of_kernels"] = by[name] / (s["event_us"] * 1e-6) / PEAK
         out["us_per_product"] = prod
         if not args.no_solve:
-            runs = {name: Solve(ctx, ops[name], n) for name in ("a_grid_potential", "b_stored_potential")}
+            names = ("a_grid_potential", "b_stored_potential") + (("e_grid_periodic", "f_stored_periodic") if args.periodic else ())
+            runs = {name: Solve(ctx, ops[name], n) for name in names}
             for s in runs.values():
                 s.cycles(3)
             rate = {name: [] for name in runs}
@@ -143,14 +162,18 @@ def main():
                     rate[name].append(s.cycles(args.cycles))
             out["iterations_per_s"] = {name: stats(v) for name, v in rate.items()}
             out["same_restart_trail"] = runs["a_grid_potential"].trail == runs["b_stored_potential"].trail
+            if args.periodic:
+                out["same_restart_trail_periodic"] = runs["e_grid_periodic"].trail == runs["f_stored_periodic"].trail
             out["blocks"] = {name: s.ws.sstep_info["blocks"] for name, s in runs.items()}
             for s in runs.values():
                 s.ws.close()
         print(json.dumps(out), flush=True)
         print("m = %d (n = %d): us per product, mean +- std [min, max] over %d rounds of %d products; fraction of 8 TB/s" % (m, n, args.rounds, args.chains * MAXDIM))
         for name, s in prod.items():
-            print("  %-20s %8.2f +- %5.2f  [%7.2f, %7.2f]   %5.1f B/row  %5.1f %%   kernels alone (HIP events) %7.2f us" % (
-                name, s["mean"], s["std"], s["min"], s["max"], s["bytes_per_product"] / n, 100 * s["hbm_fraction_at_mean"], s["event_us"]))
+            e = s["event_rounds"]
+            print("  %-20s %8.2f +- %5.2f  [%7.2f, %7.2f]   %5.1f B/row  %5.1f %%   kernels alone (HIP events) %7.2f us  [%7.2f, %7.2f]  %5.1f %%" % (
+                name, s["mean"], s["std"], s["min"], s["max"], s["bytes_per_product"] / n, 100 * s["hbm_fraction_at_mean"], e["mean"], e["min"], e["max"],
+                100 * s["hbm_fraction_of_kernels"]))
         if not args.no_solve:
             for name, s in out["iterations_per_s"].items():
                 print("  %-20s %8.0f +- %5.0f iterations/s  [%7.0f, %7.0f]" % (name, s["mean"], s["std"], s["min"], s["max"]))
