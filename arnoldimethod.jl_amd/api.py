@@ -475,7 +475,16 @@ def product_operator(*factors, ctx: Context | None = None) -> Operator:
     return op
 
 
-def _grid_args(shape, taps, potential, dtype):
+def _grid_radius(radius, periodic, wrap):
+    """The radius of a grid operator's star stencil as an int: an integer in 1...4, above 1 only with open boundaries."""
+    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= 4:
+        raise ArgumentError(f"radius must be an integer in 1...4 (the distance of the farthest neighbour along an axis), got {radius!r}")
+    if int(radius) > 1 and (periodic is not None or wrap is not None):
+        raise ArgumentError(f"periodic / wrap are supported for radius 1 only, got radius = {int(radius)}")
+    return int(radius)
+
+
+def _grid_args(shape, taps, potential, dtype, radius=1):
     """(dtype, dims, taps, potential or None) of a grid operator.  The element type is promoted like `_tridiag_args` promotes
     (ComplexF64 as soon as the taps or the potential are complex) unless `dtype` pins it; a pinned Float64 refuses imaginary parts."""
     try:
@@ -492,8 +501,9 @@ def _grid_args(shape, taps, potential, dtype):
         raise ArgumentError(f"element type must be float64 or complex128, not {dt}")
     if dt.kind == "f" and cplx and (np.any(t.imag != 0) or (v is not None and np.any(v.imag != 0))):
         raise ArgumentError("taps or potential have an imaginary part but the element type is Float64 (KS_F64)")
-    if t.shape != (2 * ndim + 1,):
-        raise DimensionMismatch(f"a {ndim}-D grid takes {2 * ndim + 1} taps in ascending column order, got shape {t.shape}")
+    if t.shape != (2 * ndim * radius + 1,):
+        of = "" if radius == 1 else f" of radius {radius}"
+        raise DimensionMismatch(f"a {ndim}-D grid{of} takes {2 * ndim * radius + 1} taps in ascending column order, got shape {t.shape}")
     t = np.ascontiguousarray(t.real if dt.kind == "f" else t, dtype=dt)
     if v is not None:
         n = math.prod(int(d) for d in dims)
@@ -537,7 +547,7 @@ def _grid_wrap_args(dims, t, v, dt, dtype, periodic, wrap):
     return dt, t, v, flags, w
 
 
-def grid_operator(shape, taps, potential=None, dtype=None, ctx: Context | None = None, periodic=None, wrap=None) -> Operator:
+def grid_operator(shape, taps, potential=None, dtype=None, ctx: Context | None = None, periodic=None, wrap=None, radius=1) -> Operator:
     """Matrix-free operator of a constant-coefficient 3-, 5- or 7-point stencil plus a per-point diagonal term on a grid
     (`ks_operator_grid`): mul!(y, A, x), src/expansion.jl:121, for A = -Laplacian + V(x) and its kin with nothing stored per
     non-zero -- 24 bytes per row and product in Float64 (16 without a potential) where a stored matrix with a varying diagonal
@@ -553,13 +563,23 @@ def grid_operator(shape, taps, potential=None, dtype=None, ctx: Context | None =
     `periodic` (`ks_operator_grid_periodic`): True, or one bool per axis in the order of `shape` -- on such an axis (extent >= 3)
     the first and the last point of a line are neighbours.  `wrap`: 2 ndim values in the order of the taps without the centre
     ([-z, -y, -x, +x, +y, +z] in 3-D), the entries of the links that cross the boundary; None = the taps (plain periodicity),
-    `extras.bloch_wrap(taps, theta)` = Bloch phases, `-taps` = antiperiodic.  The traffic per row is unchanged."""
+    `extras.bloch_wrap(taps, theta)` = Bloch phases, `-taps` = antiperiodic.  The traffic per row is unchanged.
+
+    `radius` (`ks_operator_grid_star`): an integer R in 1...4, a star stencil with neighbours at the distances 1...R along every
+    axis -- central differences of order 2 R (`extras.fd_laplacian_taps(ndim, 2 * R)`).  `taps` then holds 2 ndim R + 1 values in
+    ascending column order, [-R z ... -1 z, -R y ... -1 y, -R x ... -1 x, centre, +1 x ... +R x, +1 y ... +R y, +1 z ... +R z] in
+    3-D; boundaries are open (R > 1 together with `periodic` or `wrap` is refused).  The traffic per row is still unchanged, where
+    the stored matrix streams about 12 bytes per non-zero.  The radius is never inferred from the length of `taps`."""
+    radius = _grid_radius(radius, periodic, wrap)
     ctx = ctx or default_context()
     lib = _lib.load()
-    dt, dims, t, v = _grid_args(shape, taps, potential, dtype)
+    dt, dims, t, v = _grid_args(shape, taps, potential, dtype, radius)
     h = C.c_void_p()
     flags, w = np.zeros(dims.size, dtype=np.int32), None
-    if periodic is None and wrap is None:
+    if radius > 1:
+        check(lib.ks_operator_grid_star(ctx._h, int(dims.size), dims.ctypes.data, radius, _dtype_code(dt), t.ctypes.data,
+                                        None if v is None else v.ctypes.data, C.byref(h)))
+    elif periodic is None and wrap is None:
         check(lib.ks_operator_grid(ctx._h, int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data, None if v is None else v.ctypes.data,
                                    C.byref(h)))
     else:
@@ -571,25 +591,32 @@ def grid_operator(shape, taps, potential=None, dtype=None, ctx: Context | None =
     op = Operator(ctx, h, (n, n), dt)
     op.grid_info = dict(shape=tuple(int(d) for d in dims), taps=t.copy(), has_potential=v is not None,
                         bytes_per_row=dt.itemsize * (3 if v is not None else 2), periodic=tuple(bool(f) for f in flags),
-                        wrap=None if w is None else w.copy())
+                        wrap=None if w is None else w.copy(), radius=radius)
     return op
 
 
-def host_grid_matrix(shape, taps, potential=None, dtype=None, periodic=None, wrap=None):
+def host_grid_matrix(shape, taps, potential=None, dtype=None, periodic=None, wrap=None, radius=1):
     """The matrix that defines `grid_operator(shape, taps, potential)` as a scipy.sparse.csr_matrix (`ks_host_grid_matrix`: the host
     path, no device): ascending columns, the diagonal entry centre + potential[r] stored even where it is zero.  `periodic`, `wrap`:
-    as for `grid_operator` (`ks_host_grid_matrix_periodic`)."""
+    as for `grid_operator` (`ks_host_grid_matrix_periodic`); `radius`: as for `grid_operator` (`ks_host_grid_matrix_star`)."""
     import scipy.sparse as sp
 
+    radius = _grid_radius(radius, periodic, wrap)
     lib = _lib.load()
-    dt, dims, t, v = _grid_args(shape, taps, potential, dtype)
+    dt, dims, t, v = _grid_args(shape, taps, potential, dtype, radius)
     ext = [int(d) for d in dims] + [1] * (3 - dims.size)
     ok = all(1 <= e < 2 ** 31 for e in ext) and ext[0] * ext[1] * ext[2] < 2 ** 31 - 1
     n = ext[0] * ext[1] * ext[2] if ok else 0
     nx, ny, nz = ext if ok else (1, 1, 1)
     nnz = n + 2 * ((nx - 1) * ny * nz + nx * (ny - 1) * nz + nx * ny * (nz - 1)) if ok else 0
     got = C.c_int64()
-    if periodic is None and wrap is None:
+    if radius > 1:
+        nnz += sum(2 * max(e - d, 0) * (n // e) for e in ext for d in range(2, radius + 1)) if ok else 0
+        rowptr, colidx, val = np.zeros(n + 1, dtype=np.int64), np.zeros(max(nnz, 1), dtype=np.int32), np.zeros(max(nnz, 1), dtype=dt)
+        check(lib.ks_host_grid_matrix_star(int(dims.size), dims.ctypes.data, radius, _dtype_code(dt), t.ctypes.data,
+                                           None if v is None else v.ctypes.data, rowptr.ctypes.data, colidx.ctypes.data, val.ctypes.data,
+                                           nnz, C.byref(got)))
+    elif periodic is None and wrap is None:
         rowptr, colidx, val = np.zeros(n + 1, dtype=np.int64), np.zeros(max(nnz, 1), dtype=np.int32), np.zeros(max(nnz, 1), dtype=dt)
         check(lib.ks_host_grid_matrix(int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data, None if v is None else v.ctypes.data,
                                       rowptr.ctypes.data, colidx.ctypes.data, val.ctypes.data, nnz, C.byref(got)))

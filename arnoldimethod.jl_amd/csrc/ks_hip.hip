@@ -520,6 +520,18 @@ int ks_operator_grid(ks_ctx* ctx, int ndim, const int64_t* dims, int dtype, cons
   });
 }
 
+int ks_operator_grid_star(ks_ctx* ctx, int ndim, const int64_t* dims, int radius, int dtype, const void* taps, const void* potential,
+                          ks_operator** out) {
+  return guarded([&] {
+    KS_REQUIRE(ctx && out, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
+    KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, "ks_operator_grid_star: single-GPU contexts only (the grid is not partitioned across ranks)");
+    ctx->use();
+    *out = dtype == KS_F64 ? make_grid<double>(ctx, "ks_operator_grid_star", ndim, dims, taps, potential, nullptr, nullptr, radius)
+                           : make_grid<cd>(ctx, "ks_operator_grid_star", ndim, dims, taps, potential, nullptr, nullptr, radius);
+  });
+}
+
 int ks_operator_grid_periodic(ks_ctx* ctx, int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential,
                               const int* periodic, const void* wrap, ks_operator** out) {
   return guarded([&] {
@@ -1685,6 +1697,15 @@ int ks_host_grid_matrix(int ndim, const int64_t* dims, int dtype, const void* ta
     KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
     if (dtype == KS_F64) grid::host_matrix_entry<double>("ks_host_grid_matrix", ndim, dims, taps, potential, nullptr, nullptr, rowptr, colidx, val, cap, nnz);
     else grid::host_matrix_entry<cplx>("ks_host_grid_matrix", ndim, dims, taps, potential, nullptr, nullptr, rowptr, colidx, val, cap, nnz);
+  });
+}
+
+int ks_host_grid_matrix_star(int ndim, const int64_t* dims, int radius, int dtype, const void* taps, const void* potential, int64_t* rowptr,
+                             int32_t* colidx, void* val, int64_t cap, int64_t* nnz) {
+  return guarded([&] {
+    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
+    if (dtype == KS_F64) grid::host_matrix_star_entry<double>("ks_host_grid_matrix_star", ndim, dims, radius, taps, potential, rowptr, colidx, val, cap, nnz);
+    else grid::host_matrix_star_entry<cplx>("ks_host_grid_matrix_star", ndim, dims, radius, taps, potential, rowptr, colidx, val, cap, nnz);
   });
 }
 

@@ -219,3 +219,43 @@ def bloch_wrap(taps, theta) -> np.ndarray:
         w[ndim - 1 - a] = t[ndim - 1 - a] * np.exp(-1j * th[a])
         w[ndim + a] = t[ndim + 1 + a] * np.exp(1j * th[a])
     return w
+
+
+# 1-D weights of -d^2/dx^2 by central differences, centre first then the distances 1, 2, ...: (numerator, denominator)
+_FD_WEIGHTS = {
+    2: ((2, 1), (-1, 1)),
+    4: ((5, 2), (-4, 3), (1, 12)),
+    6: ((49, 18), (-3, 2), (3, 20), (-1, 90)),
+    8: ((205, 72), (-8, 5), (1, 5), (-8, 315), (1, 560)),
+}
+
+
+def fd_laplacian_taps(ndim, order, spacing=1.0, scale=1.0) -> np.ndarray:
+    """The taps of `scale * (-Laplacian)` by central differences of `order` 2, 4, 6 or 8 for `api.grid_operator(shape, taps, ...,
+    radius=order // 2)`: 2 ndim R + 1 Float64 values in ascending column order, [-R z ... -1 z, -R y ... -1 y, -R x ... -1 x, centre,
+    +1 x ... +R x, +1 y ... +R y, +1 z ... +R z] in 3-D.  `spacing`: the grid spacing h, a scalar or one value per axis in the order
+    of the shape (x[, y[, z]]).  The weight of distance d along axis a is scale * w_d / h_a^2 with the rational w_d rounded once;
+    the centre is the sum over the axes."""
+    if isinstance(ndim, (bool, np.bool_)) or not isinstance(ndim, (int, np.integer)) or not 1 <= int(ndim) <= 3:
+        raise api.ArgumentError(f"a grid has 1, 2 or 3 dimensions (ndim), got {ndim!r}")
+    if isinstance(order, (bool, np.bool_)) or not isinstance(order, (int, np.integer)) or int(order) not in _FD_WEIGHTS:
+        raise api.ArgumentError(f"order must be 2, 4, 6 or 8, got {order!r}")
+    ndim, order = int(ndim), int(order)
+    h = np.asarray(spacing, dtype=np.float64)
+    if h.ndim == 0:
+        h = np.full(ndim, float(h))
+    if h.shape != (ndim,):
+        raise api.DimensionMismatch(f"spacing takes a scalar or one value per axis ({ndim}), got shape {h.shape}")
+    if not np.all(np.isfinite(h)) or np.any(h <= 0):
+        raise api.ArgumentError(f"spacing must be positive and finite, got {spacing!r}")
+    R = order // 2
+    w = [num / den for num, den in _FD_WEIGHTS[order]]
+    t = np.zeros(2 * ndim * R + 1, dtype=np.float64)
+    c = ndim * R
+    for a in range(ndim):
+        f = float(scale) / (h[a] * h[a])
+        t[c] += f * w[0]
+        for d in range(1, R + 1):
+            # axis a: its -d link is entry c - a R - d, its +d link entry c + a R + d
+            t[c - a * R - d] = t[c + a * R + d] = f * w[d]
+    return t

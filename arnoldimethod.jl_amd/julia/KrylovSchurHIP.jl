@@ -266,12 +266,17 @@ end
 # `periodic`: `true`, or one flag per axis in the order of `dims` -- those axes wrap (ks_operator_grid_periodic; an extent of at least 3
 # each).  `wrap`: 2 ndim values in the order of the taps without the centre ([-z, -y, -x, +x, +y, +z] in 3-D), the entries of the links
 # that cross the cell boundary; `nothing` = the taps (plain periodicity), t e^{+-i theta} = Bloch, -taps = antiperiodic.
+# `radius` = 2, 3, 4: a star stencil with neighbours at the distances 1...radius along every axis (ks_operator_grid_star: central
+# differences of order 4, 6, 8), open boundaries only; `taps` then holds 2 ndim radius + 1 values in ascending column order,
+# [-R z ... -1 z, -R y ... -1 y, -R x ... -1 x, centre, +1 x ... +R x, +1 y ... +R y, +1 z ... +R z] in 3-D.
 function HipGridOperator(ctx::HipContext, dims::NTuple{N,Integer}, taps::AbstractVector; potential::Union{Nothing,AbstractArray} = nothing,
                          periodic::Union{Nothing,Bool,NTuple{N,Bool},AbstractVector{Bool}} = nothing,
-                         wrap::Union{Nothing,AbstractVector} = nothing) where {N}
+                         wrap::Union{Nothing,AbstractVector} = nothing, radius::Integer = 1) where {N}
     1 <= N <= 3 || throw(ArgumentError("a grid has 1, 2 or 3 dimensions"))
+    1 <= radius <= 4 || throw(ArgumentError("radius must be 1, 2, 3 or 4"))
+    (radius == 1 || (periodic === nothing && wrap === nothing)) || throw(ArgumentError("periodic / wrap take radius 1"))
     T = (eltype(taps) <: Complex || (potential !== nothing && eltype(potential) <: Complex) || (wrap !== nothing && eltype(wrap) <: Complex)) ? ComplexF64 : Float64
-    length(taps) == 2N + 1 || throw(DimensionMismatch("a $(N)-D grid takes $(2N + 1) taps"))
+    length(taps) == 2N * radius + 1 || throw(DimensionMismatch("a $(N)-D grid of radius $(radius) takes $(2N * radius + 1) taps"))
     n = prod(Int64.(dims))
     (potential === nothing || length(potential) == n) || throw(DimensionMismatch("potential must have $(n) entries"))
     d = Int64[dims...]; t = Vector{T}(taps)
@@ -287,6 +292,14 @@ function HipGridOperator(ctx::HipContext, dims::NTuple{N,Integer}, taps::Abstrac
                         (Ptr{Cvoid}, Cint, Ptr{Int64}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cint}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),
                         ctx.h, Cint(N), pointer(d), dtype_code(T), pointer(t), potential === nothing ? C_NULL : pointer(v), pointer(flags),
                         wrap === nothing ? C_NULL : pointer(w), r))
+        end
+        return _finish_operator(T, r[], n, ctx, nothing)
+    end
+    if radius > 1
+        GC.@preserve d t v begin
+            check(ccall((:ks_operator_grid_star, LIB), Cint,
+                        (Ptr{Cvoid}, Cint, Ptr{Int64}, Cint, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),
+                        ctx.h, Cint(N), pointer(d), Cint(radius), dtype_code(T), pointer(t), potential === nothing ? C_NULL : pointer(v), r))
         end
         return _finish_operator(T, r[], n, ctx, nothing)
     end

@@ -259,6 +259,25 @@ int ks_operator_grid_periodic(ks_ctx* ctx, int ndim, const int64_t* dims /* ndim
                               const void* taps /* 2*ndim+1 values of dtype */, const void* potential /* n values of dtype, or NULL */,
                               const int* periodic /* ndim flags, or NULL */, const void* wrap /* 2*ndim values of dtype, or NULL */,
                               ks_operator** out);
+/* (x) ... with a STAR stencil of radius 1...4: central differences of order 2, 4, 6, 8 (extras.fd_laplacian_taps), the stencils of
+ * real-space Schroedinger and electronic-structure codes -- mul!(y, A, x), src/expansion.jl:121, still with nothing stored per
+ * non-zero and the same compulsory traffic (24 / 16 bytes per row in Float64), where the stored matrix of a 3-D radius-4 star streams
+ * about 300.  Everything of (viii) holds, with these additions.  DEFINITION -- the operator is the matrix ks_host_grid_matrix_star
+ * returns:
+ *   radius      R, 1 <= R <= 4: neighbours at the distances 1...R along every axis
+ *   taps        2 ndim R + 1 values of `dtype` in ascending column order: in 3-D
+ *                 [-R z ... -1 z, -R y ... -1 y, -R x ... -1 x, centre, +1 x ... +R x, +1 y ... +R y, +1 z ... +R z]
+ *               (2-D and 1-D: without the z, the z and y groups); for R = 1 the layout of (viii)
+ *   boundaries  open: a tap whose neighbour i_a + d lies outside [0, m_a) is absent, no wrap-around; an axis shorter than R + 1
+ *               never has its outer taps
+ *   row         a sub-sequence of these 6 R + 1 slots; nnz = n + sum over the axes a and d = 1...R of 2 max(m_a - d, 0) n / m_a
+ *   product     every product rounded on its own and added to +0.0 in this order: bit-identical to ks_operator_csr of the matrix.
+ *               An absent tap -- outside the grid, or beyond the radius -- is not multiplied at all
+ * KS_ERR_ARGUMENT in addition: radius outside 1...4 (the message names radius); "tap k is not finite" counts k in this layout.
+ * Periodic axes take radius 1 (ix).  With radius == 1 the operator is that of ks_operator_grid: same matrix, same kernel. */
+int ks_operator_grid_star(ks_ctx* ctx, int ndim, const int64_t* dims /* ndim entries: nx[, ny[, nz]] */, int radius, int dtype,
+                          const void* taps /* 2*ndim*radius+1 values of dtype */,
+                          const void* potential /* n values of dtype, or NULL */, ks_operator** out);
 int ks_operator_destroy(ks_operator* op);
 int ks_operator_size(const ks_operator* op, int64_t* n_local, int64_t* nnz, int* dtype);
 /* Device layout chosen for a stored matrix at upload (mul!(y, A, x), src/expansion.jl:121; all layouts give bit-identical y):
@@ -639,6 +658,12 @@ int ks_host_grid_matrix(int ndim, const int64_t* dims, int dtype, const void* ta
 int ks_host_grid_matrix_periodic(int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential,
                                  const int* periodic /* ndim flags, or NULL */, const void* wrap /* 2*ndim values, or NULL */,
                                  int64_t* rowptr /* n+1 */, int32_t* colidx, void* val, int64_t cap, int64_t* nnz);
+/* ... and the matrix that DEFINES ks_operator_grid_star (mul!(y, A, x), src/expansion.jl:121): `radius` and the 2 ndim radius + 1
+ * `taps` as there, every row a sub-sequence of its 6 radius + 1 slots, *nnz = n + sum over the axes a and d = 1...radius of
+ * 2 max(m_a - d, 0) n / m_a.  With radius == 1 the arrays are those of ks_host_grid_matrix.  Same refusals as that operator, except
+ * that no context is involved. */
+int ks_host_grid_matrix_star(int ndim, const int64_t* dims, int radius, int dtype, const void* taps, const void* potential,
+                             int64_t* rowptr /* n+1 */, int32_t* colidx, void* val, int64_t cap, int64_t* nnz);
 /* The plan, the factors and the HOST apply of ks_operator_tridiag_solve without a device (docs/src/index.md:234-259: the
  * factorize / ldiv! pair of the shift-invert recipe): x[:, k] = (T - sigma I)^-1 b[:, k] for nrhs columns (column k at b + k ldb,
  * x + k ldx; b and x distinct), walking exactly the arrays the device kernels read, in their order.  Same refusals as the operator. */

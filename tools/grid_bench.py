@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The matrix-free grid operator (ks_operator_grid) against the stored layouts, in the solver's own access pattern:
 
-    python tools/grid_bench.py [--sizes 216,100] [--rounds 7] [--chains 5] [--cycles 20] [--no-solve] [--periodic]
+    python tools/grid_bench.py [--sizes 216,100] [--rounds 7] [--chains 5] [--cycles 20] [--no-solve] [--periodic] [--radius R]
 
 Float64, 7-point -Laplacian (+ a harmonic potential) on m x m x m grids.  Per size, in ONE process:
 
@@ -16,6 +16,9 @@ Float64, 7-point -Laplacian (+ a harmonic potential) on m x m x m grids.  Per si
              --periodic adds, on the torus (ks_operator_grid_periodic):
                (e) grid_operator(..., periodic=True) with the potential     24 n bytes, as (a)
                (f) csr_operator(host_grid_matrix(..., periodic=True))       the same matrix stored
+             --radius R (2, 3, 4; ks_operator_grid_star) runs (a), (b) and (c) with the star stencil of central differences of
+             order 2 R, extras.fd_laplacian_taps(3, 2 R), instead of the 7-point one: (a) and (c) still move 24 n / 16 n bytes,
+             (b) streams the 6 R + 1 entries of a row.  (d) and --periodic belong to the 7-point stencil and are left out.
              The HIP-event time is taken per round as well (`event_rounds`): its mean and max - min are what two builds are
              compared by.
   solve      iterations/s of nev = 20, mindim / maxdim = 20 / 40, :SR on (a) and (b): `cycles` timed restart cycles after 3 warm-up
@@ -117,7 +120,11 @@ def main():
     ap.add_argument("--cycles", type=int, default=20)
     ap.add_argument("--no-solve", action="store_true")
     ap.add_argument("--periodic", action="store_true", help="add (e) the periodic grid operator and (f) its stored matrix")
+    ap.add_argument("--radius", type=int, default=None, help="2, 3 or 4: (a), (b), (c) with the star stencil of order 2 R")
     args = ap.parse_args()
+    if args.radius is not None:
+        main_star(args)
+        return
     ctx = ks.Context(0)
     for m in (int(s) for s in args.sizes.split(",")):
         shape, n = (m, m, m), m ** 3
@@ -167,17 +174,70 @@ def main():
             out["blocks"] = {name: s.ws.sstep_info["blocks"] for name, s in runs.items()}
             for s in runs.values():
                 s.ws.close()
-        print(json.dumps(out), flush=True)
-        print("m = %d (n = %d): us per product, mean +- std [min, max] over %d rounds of %d products; fraction of 8 TB/s" % (m, n, args.rounds, args.chains * MAXDIM))
+        report(out, prod, m, n, args)
+        for op in ops.values():
+            op.close()
+
+
+def report(out, prod, m, n, args):
+    print(json.dumps(out), flush=True)
+    print("m = %d (n = %d): us per product, mean +- std [min, max] over %d rounds of %d products; fraction of 8 TB/s" % (m, n, args.rounds, args.chains * MAXDIM))
+    for name, s in prod.items():
+        e = s["event_rounds"]
+        print("  %-20s %8.2f +- %5.2f  [%7.2f, %7.2f]   %5.1f B/row  %5.1f %%   kernels alone (HIP events) %7.2f us  [%7.2f, %7.2f]  %5.1f %%" % (
+            name, s["mean"], s["std"], s["min"], s["max"], s["bytes_per_product"] / n, 100 * s["hbm_fraction_at_mean"], e["mean"], e["min"], e["max"],
+            100 * s["hbm_fraction_of_kernels"]))
+    if not args.no_solve:
+        for name, s in out["iterations_per_s"].items():
+            print("  %-20s %8.0f +- %5.0f iterations/s  [%7.0f, %7.0f]" % (name, s["mean"], s["std"], s["min"], s["max"]))
+    sys.stdout.flush()
+
+
+def main_star(args):
+    """--radius R: (a), (b), (c) with the star stencil of central differences of order 2 R."""
+    from arnoldimethod_jl_amd import extras
+
+    R = args.radius
+    if R not in (2, 3, 4) or args.periodic:
+        raise SystemExit("--radius takes 2, 3 or 4 and no --periodic")
+    taps = extras.fd_laplacian_taps(3, 2 * R)
+    ctx = ks.Context(0)
+    for m in (int(s) for s in args.sizes.split(",")):
+        shape, n = (m, m, m), m ** 3
+        V = ks.matrices.harmonic_potential(shape)
+        t0 = time.perf_counter()
+        A = ks.host_grid_matrix(shape, taps, V, radius=R)
+        ops = {
+            "a_grid_potential": ks.grid_operator(shape, taps, V, ctx=ctx, radius=R),
+            "b_stored_potential": ks.csr_operator(A, ctx),
+            "c_grid_plain": ks.grid_operator(shape, taps, ctx=ctx, radius=R),
+        }
+        nnz = A.nnz
+        setup_s = time.perf_counter() - t0
+        del A
+        fmt = {"b_stored_potential": ops["b_stored_potential"].format}
+        by = {"a_grid_potential": 24.0 * n, "c_grid_plain": 16.0 * n, "b_stored_potential": fmt["b_stored_potential"]["bytes_per_nnz"] * nnz + 16.0 * n}
+        out = dict(m=m, n=n, radius=R, nnz=nnz, setup_seconds=round(setup_s, 2), formats=fmt, chains=args.chains, products_per_round=args.chains * MAXDIM)
+        prod = bench_products(ctx, ops, n, args.rounds, args.chains)
         for name, s in prod.items():
-            e = s["event_rounds"]
-            print("  %-20s %8.2f +- %5.2f  [%7.2f, %7.2f]   %5.1f B/row  %5.1f %%   kernels alone (HIP events) %7.2f us  [%7.2f, %7.2f]  %5.1f %%" % (
-                name, s["mean"], s["std"], s["min"], s["max"], s["bytes_per_product"] / n, 100 * s["hbm_fraction_at_mean"], e["mean"], e["min"], e["max"],
-                100 * s["hbm_fraction_of_kernels"]))
+            s["bytes_per_product"] = by[name]
+            s["hbm_fraction_at_mean"] = by[name] / (s["mean"] * 1e-6) / PEAK
+            s["hbm_fraction_of_kernels"] = by[name] / (s["event_us"] * 1e-6) / PEAK
+        out["us_per_product"] = prod
         if not args.no_solve:
-            for name, s in out["iterations_per_s"].items():
-                print("  %-20s %8.0f +- %5.0f iterations/s  [%7.0f, %7.0f]" % (name, s["mean"], s["std"], s["min"], s["max"]))
-        sys.stdout.flush()
+            runs = {name: Solve(ctx, ops[name], n) for name in ("a_grid_potential", "b_stored_potential")}
+            for s in runs.values():
+                s.cycles(3)
+            rate = {name: [] for name in runs}
+            for _ in range(max(3, args.rounds // 2)):
+                for name, s in runs.items():
+                    rate[name].append(s.cycles(args.cycles))
+            out["iterations_per_s"] = {name: stats(v) for name, v in rate.items()}
+            out["same_restart_trail"] = runs["a_grid_potential"].trail == runs["b_stored_potential"].trail
+            out["blocks"] = {name: s.ws.sstep_info["blocks"] for name, s in runs.items()}
+            for s in runs.values():
+                s.ws.close()
+        report(out, prod, m, n, args)
         for op in ops.values():
             op.close()
 
