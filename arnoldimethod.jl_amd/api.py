@@ -631,6 +631,74 @@ def host_grid_matrix(shape, taps, potential=None, dtype=None, periodic=None, wra
     return sp.csr_matrix((val[:nnz], colidx[:nnz], rowptr), shape=(n, n))
 
 
+def _grid_coeff(dims, coeff):
+    """The cell-centred coefficient of a variable-coefficient grid operator as n contiguous Float64 values in row order."""
+    c = np.asarray(coeff)
+    if c.dtype.kind == "c":
+        raise ArgumentError("coeff must be real (one Float64 per grid point, also for ComplexF64 operators)")
+    n = math.prod(int(d) for d in dims)
+    # (an extent < 1 is the library's refusal to make, as for the potential)
+    if np.all(dims >= 1) and c.shape != (n,) and c.shape != tuple(int(d) for d in dims[::-1]):
+        raise DimensionMismatch(f"coeff must have shape {tuple(int(d) for d in dims[::-1])} (C order, x fastest) or ({n},), got {c.shape}")
+    try:
+        return np.ascontiguousarray(c.reshape(-1), dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ArgumentError(f"coeff must hold real numbers: {e}") from e
+
+
+def grid_variable_operator(shape, taps, coeff, potential=None, dtype=None, ctx: Context | None = None) -> Operator:
+    """Matrix-free operator of a 3-, 5- or 7-point stencil with a VARIABLE, cell-centred coefficient plus a per-point diagonal
+    term on a grid (`ks_operator_grid_var`): mul!(y, A, x), src/expansion.jl:121, for A = -div(c(x) grad) + V(x) and its kin --
+    heterogeneous diffusion, a position-dependent effective mass, div (1 / eps) grad -- with nothing stored per non-zero: 32 bytes
+    per row and product in Float64 (24 without a potential) where the stored matrix streams about 100.
+
+    `shape`, `taps`, `potential`, `dtype`: as for `grid_operator` (open boundaries, radius 1).  `coeff`: n real values, one per
+    grid point -- flat in row order, or an array of shape (nz, ny, nx) / (ny, nx) in C order; always Float64, also for ComplexF64
+    operators.  The entry of the link from row r to its in-grid neighbour s in direction k is fl(0.5 taps[k] * fl(c[r] + c[s]));
+    the diagonal entry is centre + potential[r].  The operator is exactly the matrix `host_grid_variable_matrix` returns, and its
+    products have the bits `csr_operator` of that matrix gives; with c == 1 it is `grid_operator(shape, taps, potential)`.
+
+    The diffusion operator -div(c grad) + V:  `taps, diagonal = extras.diffusion_terms(shape, coeff, spacing, V, boundary)`, then
+    `grid_variable_operator(shape, taps, coeff, potential=diagonal)`.
+
+    `operator.grid_info`: shape, taps, has_potential, variable=True, bytes_per_row."""
+    ctx = ctx or default_context()
+    lib = _lib.load()
+    dt, dims, t, v = _grid_args(shape, taps, potential, dtype)
+    c = _grid_coeff(dims, coeff)
+    h = C.c_void_p()
+    check(lib.ks_operator_grid_var(ctx._h, int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data, c.ctypes.data,
+                                   None if v is None else v.ctypes.data, C.byref(h)))
+    n = math.prod(int(d) for d in dims)
+    op = Operator(ctx, h, (n, n), dt)
+    op.grid_info = dict(shape=tuple(int(d) for d in dims), taps=t.copy(), has_potential=v is not None, variable=True,
+                        bytes_per_row=dt.itemsize * (3 if v is not None else 2) + 8)
+    return op
+
+
+def host_grid_variable_matrix(shape, taps, coeff, potential=None, dtype=None):
+    """The matrix that defines `grid_variable_operator(shape, taps, coeff, potential)` as a scipy.sparse.csr_matrix
+    (`ks_host_grid_var_matrix`: the host path, no device): ascending columns, off-diagonal entries fl(0.5 taps[k] * fl(c[r] + c[s])),
+    the diagonal entry centre + potential[r] stored even where it is zero."""
+    import scipy.sparse as sp
+
+    lib = _lib.load()
+    dt, dims, t, v = _grid_args(shape, taps, potential, dtype)
+    c = _grid_coeff(dims, coeff)
+    ext = [int(d) for d in dims] + [1] * (3 - dims.size)
+    ok = all(1 <= e < 2 ** 31 for e in ext) and ext[0] * ext[1] * ext[2] < 2 ** 31 - 1
+    n = ext[0] * ext[1] * ext[2] if ok else 0
+    nx, ny, nz = ext if ok else (1, 1, 1)
+    nnz = n + 2 * ((nx - 1) * ny * nz + nx * (ny - 1) * nz + nx * ny * (nz - 1)) if ok else 0
+    got = C.c_int64()
+    rowptr, colidx, val = np.zeros(n + 1, dtype=np.int64), np.zeros(max(nnz, 1), dtype=np.int32), np.zeros(max(nnz, 1), dtype=dt)
+    check(lib.ks_host_grid_var_matrix(int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data, c.ctypes.data,
+                                      None if v is None else v.ctypes.data, rowptr.ctypes.data, colidx.ctypes.data, val.ctypes.data,
+                                      nnz, C.byref(got)))
+    assert got.value == nnz == rowptr[-1]
+    return sp.csr_matrix((val[:nnz], colidx[:nnz], rowptr), shape=(n, n))
+
+
 def host_operator(fn, n: int, dtype=np.float64, ctx: Context | None = None) -> Operator:
     """Opaque host operator: `fn(y, x)` fills y = A*x on numpy views (a LinearMap wrapping ldiv!,
     docs/src/index.md:246-249).  Columns are staged over PCIe by the library."""

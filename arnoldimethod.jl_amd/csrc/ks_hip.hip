@@ -42,6 +42,7 @@ using ksd::kBlock;
 #include "ks_tridiag.hpp"    // tridiagonal shift-invert operator: factored once on the host (ks_tridiag_plan.hpp), applied in HBM
 #include "ks_product.hpp"    // product of operators: generalized problems composed in HBM
 #include "ks_grid.hpp"       // matrix-free grid operator: stencil taps in the kernel arguments plus a per-point diagonal
+#include "ks_grid_var.hpp"   // ... with a cell-centred coefficient: the link entries formed in registers from c
 #include "ks_workspace.hpp"  // ks_workspace, launch helpers, expansion, rotations
 #include "ks_block.hpp"      // s-step (block) expansion: launchers, shifts, block sizes
 #include "ks_backend.hpp"    // HipBackend, residual checks, placement search
@@ -541,6 +542,18 @@ int ks_operator_grid_periodic(ks_ctx* ctx, int ndim, const int64_t* dims, int dt
     ctx->use();
     *out = dtype == KS_F64 ? make_grid<double>(ctx, "ks_operator_grid_periodic", ndim, dims, taps, potential, periodic, wrap)
                            : make_grid<cd>(ctx, "ks_operator_grid_periodic", ndim, dims, taps, potential, periodic, wrap);
+  });
+}
+
+int ks_operator_grid_var(ks_ctx* ctx, int ndim, const int64_t* dims, int dtype, const void* taps, const double* coeff, const void* potential,
+                         ks_operator** out) {
+  return guarded([&] {
+    KS_REQUIRE(ctx && out, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
+    KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, "ks_operator_grid_var: single-GPU contexts only (the grid is not partitioned across ranks)");
+    ctx->use();
+    *out = dtype == KS_F64 ? make_grid_var<double>(ctx, "ks_operator_grid_var", ndim, dims, taps, coeff, potential)
+                           : make_grid_var<cd>(ctx, "ks_operator_grid_var", ndim, dims, taps, coeff, potential);
   });
 }
 
@@ -1715,6 +1728,15 @@ int ks_host_grid_matrix_periodic(int ndim, const int64_t* dims, int dtype, const
     KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
     if (dtype == KS_F64) grid::host_matrix_entry<double>("ks_host_grid_matrix_periodic", ndim, dims, taps, potential, periodic, wrap, rowptr, colidx, val, cap, nnz);
     else grid::host_matrix_entry<cplx>("ks_host_grid_matrix_periodic", ndim, dims, taps, potential, periodic, wrap, rowptr, colidx, val, cap, nnz);
+  });
+}
+
+int ks_host_grid_var_matrix(int ndim, const int64_t* dims, int dtype, const void* taps, const double* coeff, const void* potential,
+                            int64_t* rowptr, int32_t* colidx, void* val, int64_t cap, int64_t* nnz) {
+  return guarded([&] {
+    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
+    if (dtype == KS_F64) grid::host_var_matrix_entry<double>("ks_host_grid_var_matrix", ndim, dims, taps, coeff, potential, rowptr, colidx, val, cap, nnz);
+    else grid::host_var_matrix_entry<cplx>("ks_host_grid_var_matrix", ndim, dims, taps, coeff, potential, rowptr, colidx, val, cap, nnz);
   });
 }
 

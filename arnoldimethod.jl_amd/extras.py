@@ -259,3 +259,50 @@ def fd_laplacian_taps(ndim, order, spacing=1.0, scale=1.0) -> np.ndarray:
             # axis a: its -d link is entry c - a R - d, its +d link entry c + a R + d
             t[c - a * R - d] = t[c + a * R + d] = f * w[d]
     return t
+
+
+def diffusion_terms(shape, coeff, spacing=1.0, potential=None, boundary="dirichlet"):
+    """(taps, diagonal) of the diffusion operator -div(c grad) + V on a grid with the cell-centred coefficient `coeff`, for
+    `api.grid_variable_operator`:
+
+        taps, diagonal = diffusion_terms(shape, coeff, spacing, V, boundary)
+        op = api.grid_variable_operator(shape, taps, coeff, potential=diagonal)
+
+    `taps`: -1 / h_a^2 on the two links of axis a, centre 0 (`spacing`: the grid spacing h, a scalar or one value per axis in the
+    order of the shape, as in `fd_laplacian_taps`), so that the link from r to s carries e = fl(0.5 t_k * fl(c[r] + c[s])), minus the
+    arithmetic mean of the two coefficients over h^2.  `diagonal[r] = (0.0 - e_1 - e_2 ...) + V[r]`, the e_k of the row in slot order
+    (-z, -y, -x, +x, +y, +z), flat in row order.  A direction whose neighbour lies outside the grid: `boundary="dirichlet"` takes
+    c[s] := c[r] (a ghost cell with the boundary cell's coefficient and the value 0: with c == 1 and spacing 1 exactly the
+    [-1 ... 2 ndim ... -1] Laplacian), `"neumann"` leaves the term out (no flux: the row sums vanish up to rounding).  Plain numpy,
+    no device."""
+    if boundary not in ("dirichlet", "neumann"):
+        raise api.ArgumentError(f"boundary must be 'dirichlet' or 'neumann', got {boundary!r}")
+    try:
+        ndim = int(np.atleast_1d(np.asarray(shape)).size)
+    except (TypeError, ValueError) as e:
+        raise api.ArgumentError(f"shape must hold 1 to 3 integer extents: {shape!r}") from e
+    if not 1 <= ndim <= 3:
+        raise api.ArgumentError(f"a grid has 1, 2 or 3 dimensions (ndim), shape = {shape!r}")
+    taps = fd_laplacian_taps(ndim, 2, spacing)
+    taps[ndim] = 0.0
+    _dt, dims, _t, v = api._grid_args(shape, taps, potential, None)
+    if np.any(dims < 1):
+        raise api.ArgumentError(f"every extent must be at least 1, shape = {shape!r}")
+    c = api._grid_coeff(dims, coeff)
+    ext = [int(d) for d in dims] + [1] * (3 - ndim)
+    nx, ny, nz = ext
+    idx = np.arange(nx * ny * nz)
+    pos = (idx % nx, (idx // nx) % ny, idx // (nx * ny))
+    stride = (1, nx, nx * ny)
+    d = np.zeros(idx.size, dtype=np.float64)
+    # slot order: -z, -y, -x, then +x, +y, +z; axis a has its - link at tap ndim - 1 - a and its + link at tap ndim + 1 + a
+    for sign, axes in ((-1, range(ndim - 1, -1, -1)), (1, range(ndim))):
+        for a in axes:
+            has = pos[a] > 0 if sign < 0 else pos[a] < ext[a] - 1
+            cs = c.copy()
+            cs[has] = c[idx[has] + sign * stride[a]]
+            e = (0.5 * taps[ndim + sign * (1 + a)]) * (c + cs)
+            if boundary == "neumann":
+                e = np.where(has, e, 0.0)
+            d = d - e
+    return taps, (d if v is None else d + v)

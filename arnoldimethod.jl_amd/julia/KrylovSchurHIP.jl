@@ -46,7 +46,7 @@ using LinearAlgebra, SparseArrays, Random
 import ArnoldiMethod
 import ArnoldiMethod: ArnoldiWorkspace, PartialSchur
 
-export HipContext, HipOperator, HipTridiagonalSolve, HipTridiagonalPencil, HipProduct, HipGridOperator, tridiag_info, HipWorkspace, HipBasis, HipColumn, HipColumns, hip_partialschur, hip_partialschur!, hip_partialeigen, set_sstep!, relation_breaks
+export HipContext, HipOperator, HipTridiagonalSolve, HipTridiagonalPencil, HipProduct, HipGridOperator, HipGridVariableOperator, tridiag_info, HipWorkspace, HipBasis, HipColumn, HipColumns, hip_partialschur, hip_partialschur!, hip_partialeigen, set_sstep!, relation_breaks
 
 const LIB = get(ENV, "KSCHUR_LIB", joinpath(@__DIR__, "..", "libkschur_hip.so"))
 
@@ -307,6 +307,30 @@ function HipGridOperator(ctx::HipContext, dims::NTuple{N,Integer}, taps::Abstrac
         check(ccall((:ks_operator_grid, LIB), Cint,
                     (Ptr{Cvoid}, Cint, Ptr{Int64}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),
                     ctx.h, Cint(N), pointer(d), dtype_code(T), pointer(t), potential === nothing ? C_NULL : pointer(v), r))
+    end
+    _finish_operator(T, r[], n, ctx, nothing)
+end
+
+# ... with a VARIABLE, cell-centred coefficient (ks_operator_grid_var): A = -div(c(x) grad) + V(x) and its kin, the off-diagonal entry of
+# the link from row r to its neighbour s in direction k being fl(0.5 taps[k] * fl(c[r] + c[s])), formed in registers -- still nothing stored
+# per non-zero.  `coeff`: one real value per grid point (an `Array` of size `dims`, or a vector in row order), Float64 also for ComplexF64
+# operators; `dims`, `taps`, `potential` as for HipGridOperator (open boundaries, radius 1).  The products have the bits of the stored
+# matrix with the same entries.
+function HipGridVariableOperator(ctx::HipContext, dims::NTuple{N,Integer}, taps::AbstractVector, coeff::AbstractArray{<:Real};
+                                 potential::Union{Nothing,AbstractArray} = nothing) where {N}
+    1 <= N <= 3 || throw(ArgumentError("a grid has 1, 2 or 3 dimensions"))
+    T = (eltype(taps) <: Complex || (potential !== nothing && eltype(potential) <: Complex)) ? ComplexF64 : Float64
+    length(taps) == 2N + 1 || throw(DimensionMismatch("a $(N)-D grid takes $(2N + 1) taps"))
+    n = prod(Int64.(dims))
+    length(coeff) == n || throw(DimensionMismatch("coeff must have $(n) entries"))
+    (potential === nothing || length(potential) == n) || throw(DimensionMismatch("potential must have $(n) entries"))
+    d = Int64[dims...]; t = Vector{T}(taps); c = Vector{Float64}(vec(coeff))
+    v = potential === nothing ? T[] : Vector{T}(vec(potential))
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve d t c v begin
+        check(ccall((:ks_operator_grid_var, LIB), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{Int64}, Cint, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),
+                    ctx.h, Cint(N), pointer(d), dtype_code(T), pointer(t), pointer(c), potential === nothing ? C_NULL : pointer(v), r))
     end
     _finish_operator(T, r[], n, ctx, nothing)
 end

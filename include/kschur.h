@@ -278,6 +278,28 @@ int ks_operator_grid_periodic(ks_ctx* ctx, int ndim, const int64_t* dims /* ndim
 int ks_operator_grid_star(ks_ctx* ctx, int ndim, const int64_t* dims /* ndim entries: nx[, ny[, nz]] */, int radius, int dtype,
                           const void* taps /* 2*ndim*radius+1 values of dtype */,
                           const void* potential /* n values of dtype, or NULL */, ks_operator** out);
+/* (xi) ... with a VARIABLE coefficient: A = -div(c(x) grad) + V(x) -- heterogeneous diffusion, a position-dependent effective mass,
+ * div (1 / eps) grad in photonics, variable-density acoustics -- mul!(y, A, x), src/expansion.jl:121, still with nothing stored per
+ * non-zero although the off-diagonal entries vary from link to link: the coefficient is cell-centred, one Float64 per grid point, and
+ * the link entries are formed in registers.  A product moves x, c, the diagonal and y once: 32 bytes per row in Float64 (24 without a
+ * potential), 56 / 40 in ComplexF64, where the stored matrix streams about 100.  Grid, row numbering, dims, ndim, dtype, taps and
+ * potential as in (viii), with these additions.  DEFINITION -- the operator is the matrix ks_host_grid_var_matrix returns:
+ *   coeff       n Float64 values, one per grid point in row order; always REAL, also for KS_C64; finite, no sign requirement
+ *   half taps   h_k = 0.5 t_k for the six off-diagonal slots, computed once on the host (componentwise for ComplexF64)
+ *   entry       of the link from row r to its in-grid neighbour s in direction k:  A[r, s] = fl(h_k * fl(c[r] + c[s]))  -- one
+ *               Float64 addition, rounded, then one multiplication, rounded; ComplexF64: the two real multiplications
+ *               (h_k.re * m, h_k.im * m).  A link whose neighbour lies outside the grid is absent, as in (viii)
+ *   diagonal    centre + potential[r] as in (viii), stored even where it is zero; potential == NULL: centre.  A diffusion operator
+ *               passes centre 0 and its whole diagonal as the potential (extras.diffusion_terms)
+ *   row         the 7 slots -z, -y, -x, centre, +x, +y, +z; nnz as in (viii)
+ *   product     every product A[r, s] x[s] rounded on its own and added to +0.0 in slot order, an absent link not multiplied at all:
+ *               bit-identical to ks_operator_csr of the matrix.  With c == 1 the matrix is bit for bit that of ks_host_grid_matrix
+ *               (0.5 t * 2 is exact)
+ * KS_ERR_ARGUMENT as in (viii), and in addition: coeff == NULL, "coefficient entry k is not finite".  ks_operator_size reports n and
+ * nnz, ks_operator_format 0 / 0 / -1.  The Newton step of the s-step expansion is one launch of the same kernel, as in (viii). */
+int ks_operator_grid_var(ks_ctx* ctx, int ndim, const int64_t* dims /* ndim entries: nx[, ny[, nz]] */, int dtype,
+                         const void* taps /* 2*ndim+1 values of dtype */, const double* coeff /* n values */,
+                         const void* potential /* n values of dtype, or NULL */, ks_operator** out);
 int ks_operator_destroy(ks_operator* op);
 int ks_operator_size(const ks_operator* op, int64_t* n_local, int64_t* nnz, int* dtype);
 /* Device layout chosen for a stored matrix at upload (mul!(y, A, x), src/expansion.jl:121; all layouts give bit-identical y):
@@ -664,6 +686,12 @@ int ks_host_grid_matrix_periodic(int ndim, const int64_t* dims, int dtype, const
  * that no context is involved. */
 int ks_host_grid_matrix_star(int ndim, const int64_t* dims, int radius, int dtype, const void* taps, const void* potential,
                              int64_t* rowptr /* n+1 */, int32_t* colidx, void* val, int64_t cap, int64_t* nnz);
+/* ... and the matrix that DEFINES ks_operator_grid_var (mul!(y, A, x), src/expansion.jl:121): `coeff` as there, the off-diagonal entries
+ * fl(0.5 t_k * fl(c[r] + c[s])), every row a sub-sequence of the 7 slots, *nnz as for ks_host_grid_matrix (also reported when cap is
+ * too small).  With c == 1 the arrays are those of ks_host_grid_matrix.  Same refusals as that operator, except that no context is
+ * involved. */
+int ks_host_grid_var_matrix(int ndim, const int64_t* dims, int dtype, const void* taps, const double* coeff, const void* potential,
+                            int64_t* rowptr /* n+1 */, int32_t* colidx, void* val, int64_t cap, int64_t* nnz);
 /* The plan, the factors and the HOST apply of ks_operator_tridiag_solve without a device (docs/src/index.md:234-259: the
  * factorize / ldiv! pair of the shift-invert recipe): x[:, k] = (T - sigma I)^-1 b[:, k] for nrhs columns (column k at b + k ldb,
  * x + k ldx; b and x distinct), walking exactly the arrays the device kernels read, in their order.  Same refusals as the operator. */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The matrix-free grid operator (ks_operator_grid) against the stored layouts, in the solver's own access pattern:
 
-    python tools/grid_bench.py [--sizes 216,100] [--rounds 7] [--chains 5] [--cycles 20] [--no-solve] [--periodic] [--radius R]
+    python tools/grid_bench.py [--sizes 216,100] [--rounds 7] [--chains 5] [--cycles 20] [--no-solve] [--periodic] [--radius R] [--variable]
 
 Float64, 7-point -Laplacian (+ a harmonic potential) on m x m x m grids.  Per size, in ONE process:
 
@@ -19,6 +19,13 @@ Float64, 7-point -Laplacian (+ a harmonic potential) on m x m x m grids.  Per si
              --radius R (2, 3, 4; ks_operator_grid_star) runs (a), (b) and (c) with the star stencil of central differences of
              order 2 R, extras.fd_laplacian_taps(3, 2 R), instead of the 7-point one: (a) and (c) still move 24 n / 16 n bytes,
              (b) streams the 6 R + 1 entries of a row.  (d) and --periodic belong to the 7-point stencil and are left out.
+             --variable (ks_operator_grid_var) runs the variable-coefficient operator -div(c grad) + V, c a smooth field with a jump
+             (extras.diffusion_terms, Dirichlet), in the same rounds as today's constant-coefficient operator, the floor:
+               (a) grid_variable_operator with the diagonal        32 n bytes
+               (b) csr_operator(host_grid_variable_matrix(...))    the same matrix stored: the only way to run it without (a)
+               (c) grid_variable_operator without a diagonal       24 n bytes
+               (d) grid_operator with a potential                  24 n bytes: (a) of the plain run, the constant-coefficient floor
+             and the solve on (a) and (b).
              The HIP-event time is taken per round as well (`event_rounds`): its mean and max - min are what two builds are
              compared by.
   solve      iterations/s of nev = 20, mindim / maxdim = 20 / 40, :SR on (a) and (b): `cycles` timed restart cycles after 3 warm-up
@@ -121,7 +128,11 @@ def main():
     ap.add_argument("--no-solve", action="store_true")
     ap.add_argument("--periodic", action="store_true", help="add (e) the periodic grid operator and (f) its stored matrix")
     ap.add_argument("--radius", type=int, default=None, help="2, 3 or 4: (a), (b), (c) with the star stencil of order 2 R")
+    ap.add_argument("--variable", action="store_true", help="the variable-coefficient operator against its stored matrix and the constant-coefficient floor")
     args = ap.parse_args()
+    if args.variable:
+        main_variable(args)
+        return
     if args.radius is not None:
         main_star(args)
         return
@@ -234,6 +245,65 @@ def main_star(args):
                     rate[name].append(s.cycles(args.cycles))
             out["iterations_per_s"] = {name: stats(v) for name, v in rate.items()}
             out["same_restart_trail"] = runs["a_grid_potential"].trail == runs["b_stored_potential"].trail
+            out["blocks"] = {name: s.ws.sstep_info["blocks"] for name, s in runs.items()}
+            for s in runs.values():
+                s.ws.close()
+        report(out, prod, m, n, args)
+        for op in ops.values():
+            op.close()
+
+
+def jump_coefficient(shape):
+    """1 + 0.5 sin(0.7 x + 0.3 y) cos(0.5 z) + 1.5 [x > nx // 2] on the point indices, flat in row order: smooth, with a jump."""
+    nx, ny, nz = shape
+    z, y, x = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij", sparse=True)
+    return (1.0 + 0.5 * np.sin(0.7 * x + 0.3 * y) * np.cos(0.5 * z) + 1.5 * (x > nx // 2)).ravel()
+
+
+def main_variable(args):
+    """--variable: the variable-coefficient operator with (a) and without (c) its diagonal, its stored matrix (b), and the
+    constant-coefficient operator with a potential (d) as the floor, in the same rounds; the solve on (a) and (b)."""
+    from arnoldimethod_jl_amd import extras
+
+    if args.periodic or args.radius is not None:
+        raise SystemExit("--variable takes no --periodic and no --radius")
+    ctx = ks.Context(0)
+    for m in (int(s) for s in args.sizes.split(",")):
+        shape, n = (m, m, m), m ** 3
+        V = ks.matrices.harmonic_potential(shape)
+        c = jump_coefficient(shape)
+        t0 = time.perf_counter()
+        taps, diag = extras.diffusion_terms(shape, c, potential=V)
+        A = ks.host_grid_variable_matrix(shape, taps, c, diag)
+        ops = {
+            "a_var_diagonal": ks.grid_variable_operator(shape, taps, c, diag, ctx=ctx),
+            "b_stored_variable": ks.csr_operator(A, ctx),
+            "c_var_plain": ks.grid_variable_operator(shape, LAPLACE, c, ctx=ctx),
+            "d_grid_potential": ks.grid_operator(shape, LAPLACE, V, ctx=ctx),
+        }
+        nnz = A.nnz
+        setup_s = time.perf_counter() - t0
+        del A
+        fmt = {"b_stored_variable": ops["b_stored_variable"].format}
+        by = {"a_var_diagonal": 32.0 * n, "c_var_plain": 24.0 * n, "d_grid_potential": 24.0 * n,
+              "b_stored_variable": fmt["b_stored_variable"]["bytes_per_nnz"] * nnz + 16.0 * n}
+        out = dict(m=m, n=n, variable=True, nnz=nnz, setup_seconds=round(setup_s, 2), formats=fmt, chains=args.chains, products_per_round=args.chains * MAXDIM)
+        prod = bench_products(ctx, ops, n, args.rounds, args.chains)
+        for name, s in prod.items():
+            s["bytes_per_product"] = by[name]
+            s["hbm_fraction_at_mean"] = by[name] / (s["mean"] * 1e-6) / PEAK
+            s["hbm_fraction_of_kernels"] = by[name] / (s["event_us"] * 1e-6) / PEAK
+        out["us_per_product"] = prod
+        if not args.no_solve:
+            runs = {name: Solve(ctx, ops[name], n) for name in ("a_var_diagonal", "b_stored_variable")}
+            for s in runs.values():
+                s.cycles(3)
+            rate = {name: [] for name in runs}
+            for _ in range(max(3, args.rounds // 2)):
+                for name, s in runs.items():
+                    rate[name].append(s.cycles(args.cycles))
+            out["iterations_per_s"] = {name: stats(v) for name, v in rate.items()}
+            out["same_restart_trail"] = runs["a_var_diagonal"].trail == runs["b_stored_variable"].trail
             out["blocks"] = {name: s.ws.sstep_info["blocks"] for name, s in runs.items()}
             for s in runs.values():
                 s.ws.close()
