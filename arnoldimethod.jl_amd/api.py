@@ -547,6 +547,37 @@ def _grid_wrap_args(dims, t, v, dt, dtype, periodic, wrap):
     return dt, t, v, flags, w
 
 
+def _grid_operator(ctx, h, dims, dt, t, v, extra_bytes=0, **info) -> Operator:
+    """The Operator of a grid operator's handle with its `grid_info`: shape, taps, has_potential, bytes_per_row and what `info` adds."""
+    n = math.prod(int(d) for d in dims)
+    op = Operator(ctx, h, (n, n), dt)
+    op.grid_info = dict(shape=tuple(int(d) for d in dims), taps=t.copy(), has_potential=v is not None,
+                        bytes_per_row=dt.itemsize * (3 if v is not None else 2) + extra_bytes, **info)
+    return op
+
+
+def _grid_nnz(dims, radius=1, flags=()):
+    """(n, nnz) of a grid matrix: the diagonal, the links of distance 1...radius and the two wrap links per line of a periodic axis.
+    (0, 0) for a shape that the library refuses (so do extents below 3 on a periodic axis: the count is then never used)."""
+    ext = [int(d) for d in dims]
+    n = math.prod(ext)
+    if not (all(1 <= e < 2 ** 31 for e in ext) and n < 2 ** 31 - 1):
+        return 0, 0
+    nnz = n + sum(2 * max(e - d, 0) * (n // e) for e in ext for d in range(1, radius + 1))
+    return n, nnz + sum(2 * (n // e) for e, f in zip(ext, flags) if f)
+
+
+def _host_grid_csr(entry, n, nnz, dt, *args):
+    """The scipy.sparse.csr_matrix one of the `ks_host_grid_*` entries fills: `args` are its arguments in front of the arrays."""
+    import scipy.sparse as sp
+
+    got = C.c_int64()
+    rowptr, colidx, val = np.zeros(n + 1, dtype=np.int64), np.zeros(max(nnz, 1), dtype=np.int32), np.zeros(max(nnz, 1), dtype=dt)
+    check(entry(*args, rowptr.ctypes.data, colidx.ctypes.data, val.ctypes.data, nnz, C.byref(got)))
+    assert got.value == nnz == rowptr[-1]
+    return sp.csr_matrix((val[:nnz], colidx[:nnz], rowptr), shape=(n, n))
+
+
 def grid_operator(shape, taps, potential=None, dtype=None, ctx: Context | None = None, periodic=None, wrap=None, radius=1) -> Operator:
     """Matrix-free operator of a constant-coefficient 3-, 5- or 7-point stencil plus a per-point diagonal term on a grid
     (`ks_operator_grid`): mul!(y, A, x), src/expansion.jl:121, for A = -Laplacian + V(x) and its kin with nothing stored per
@@ -587,48 +618,28 @@ def grid_operator(shape, taps, potential=None, dtype=None, ctx: Context | None =
         check(lib.ks_operator_grid_periodic(ctx._h, int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data,
                                             None if v is None else v.ctypes.data, flags.ctypes.data, None if w is None else w.ctypes.data,
                                             C.byref(h)))
-    n = math.prod(int(d) for d in dims)
-    op = Operator(ctx, h, (n, n), dt)
-    op.grid_info = dict(shape=tuple(int(d) for d in dims), taps=t.copy(), has_potential=v is not None,
-                        bytes_per_row=dt.itemsize * (3 if v is not None else 2), periodic=tuple(bool(f) for f in flags),
-                        wrap=None if w is None else w.copy(), radius=radius)
-    return op
+    return _grid_operator(ctx, h, dims, dt, t, v, periodic=tuple(bool(f) for f in flags), wrap=None if w is None else w.copy(), radius=radius)
 
 
 def host_grid_matrix(shape, taps, potential=None, dtype=None, periodic=None, wrap=None, radius=1):
     """The matrix that defines `grid_operator(shape, taps, potential)` as a scipy.sparse.csr_matrix (`ks_host_grid_matrix`: the host
     path, no device): ascending columns, the diagonal entry centre + potential[r] stored even where it is zero.  `periodic`, `wrap`:
     as for `grid_operator` (`ks_host_grid_matrix_periodic`); `radius`: as for `grid_operator` (`ks_host_grid_matrix_star`)."""
-    import scipy.sparse as sp
-
     radius = _grid_radius(radius, periodic, wrap)
     lib = _lib.load()
     dt, dims, t, v = _grid_args(shape, taps, potential, dtype, radius)
-    ext = [int(d) for d in dims] + [1] * (3 - dims.size)
-    ok = all(1 <= e < 2 ** 31 for e in ext) and ext[0] * ext[1] * ext[2] < 2 ** 31 - 1
-    n = ext[0] * ext[1] * ext[2] if ok else 0
-    nx, ny, nz = ext if ok else (1, 1, 1)
-    nnz = n + 2 * ((nx - 1) * ny * nz + nx * (ny - 1) * nz + nx * ny * (nz - 1)) if ok else 0
-    got = C.c_int64()
+    head = (int(dims.size), dims.ctypes.data)
     if radius > 1:
-        nnz += sum(2 * max(e - d, 0) * (n // e) for e in ext for d in range(2, radius + 1)) if ok else 0
-        rowptr, colidx, val = np.zeros(n + 1, dtype=np.int64), np.zeros(max(nnz, 1), dtype=np.int32), np.zeros(max(nnz, 1), dtype=dt)
-        check(lib.ks_host_grid_matrix_star(int(dims.size), dims.ctypes.data, radius, _dtype_code(dt), t.ctypes.data,
-                                           None if v is None else v.ctypes.data, rowptr.ctypes.data, colidx.ctypes.data, val.ctypes.data,
-                                           nnz, C.byref(got)))
-    elif periodic is None and wrap is None:
-        rowptr, colidx, val = np.zeros(n + 1, dtype=np.int64), np.zeros(max(nnz, 1), dtype=np.int32), np.zeros(max(nnz, 1), dtype=dt)
-        check(lib.ks_host_grid_matrix(int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data, None if v is None else v.ctypes.data,
-                                      rowptr.ctypes.data, colidx.ctypes.data, val.ctypes.data, nnz, C.byref(got)))
-    else:
-        dt, t, v, flags, w = _grid_wrap_args(dims, t, v, dt, dtype, periodic, wrap)
-        nnz += sum(2 * (n // e) for e, f in zip(ext, flags) if f) if ok else 0   # (an extent < 3: the library's refusal to make)
-        rowptr, colidx, val = np.zeros(n + 1, dtype=np.int64), np.zeros(max(nnz, 1), dtype=np.int32), np.zeros(max(nnz, 1), dtype=dt)
-        check(lib.ks_host_grid_matrix_periodic(int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data,
-                                               None if v is None else v.ctypes.data, flags.ctypes.data, None if w is None else w.ctypes.data,
-                                               rowptr.ctypes.data, colidx.ctypes.data, val.ctypes.data, nnz, C.byref(got)))
-    assert got.value == nnz == rowptr[-1]
-    return sp.csr_matrix((val[:nnz], colidx[:nnz], rowptr), shape=(n, n))
+        n, nnz = _grid_nnz(dims, radius)
+        return _host_grid_csr(lib.ks_host_grid_matrix_star, n, nnz, dt, *head, radius, _dtype_code(dt), t.ctypes.data,
+                              None if v is None else v.ctypes.data)
+    if periodic is None and wrap is None:
+        n, nnz = _grid_nnz(dims)
+        return _host_grid_csr(lib.ks_host_grid_matrix, n, nnz, dt, *head, _dtype_code(dt), t.ctypes.data, None if v is None else v.ctypes.data)
+    dt, t, v, flags, w = _grid_wrap_args(dims, t, v, dt, dtype, periodic, wrap)
+    n, nnz = _grid_nnz(dims, 1, flags)
+    return _host_grid_csr(lib.ks_host_grid_matrix_periodic, n, nnz, dt, *head, _dtype_code(dt), t.ctypes.data,
+                          None if v is None else v.ctypes.data, flags.ctypes.data, None if w is None else w.ctypes.data)
 
 
 def _grid_coeff(dims, coeff):
@@ -669,34 +680,19 @@ def grid_variable_operator(shape, taps, coeff, potential=None, dtype=None, ctx: 
     h = C.c_void_p()
     check(lib.ks_operator_grid_var(ctx._h, int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data, c.ctypes.data,
                                    None if v is None else v.ctypes.data, C.byref(h)))
-    n = math.prod(int(d) for d in dims)
-    op = Operator(ctx, h, (n, n), dt)
-    op.grid_info = dict(shape=tuple(int(d) for d in dims), taps=t.copy(), has_potential=v is not None, variable=True,
-                        bytes_per_row=dt.itemsize * (3 if v is not None else 2) + 8)
-    return op
+    return _grid_operator(ctx, h, dims, dt, t, v, extra_bytes=8, variable=True)
 
 
 def host_grid_variable_matrix(shape, taps, coeff, potential=None, dtype=None):
     """The matrix that defines `grid_variable_operator(shape, taps, coeff, potential)` as a scipy.sparse.csr_matrix
     (`ks_host_grid_var_matrix`: the host path, no device): ascending columns, off-diagonal entries fl(0.5 taps[k] * fl(c[r] + c[s])),
     the diagonal entry centre + potential[r] stored even where it is zero."""
-    import scipy.sparse as sp
-
     lib = _lib.load()
     dt, dims, t, v = _grid_args(shape, taps, potential, dtype)
     c = _grid_coeff(dims, coeff)
-    ext = [int(d) for d in dims] + [1] * (3 - dims.size)
-    ok = all(1 <= e < 2 ** 31 for e in ext) and ext[0] * ext[1] * ext[2] < 2 ** 31 - 1
-    n = ext[0] * ext[1] * ext[2] if ok else 0
-    nx, ny, nz = ext if ok else (1, 1, 1)
-    nnz = n + 2 * ((nx - 1) * ny * nz + nx * (ny - 1) * nz + nx * ny * (nz - 1)) if ok else 0
-    got = C.c_int64()
-    rowptr, colidx, val = np.zeros(n + 1, dtype=np.int64), np.zeros(max(nnz, 1), dtype=np.int32), np.zeros(max(nnz, 1), dtype=dt)
-    check(lib.ks_host_grid_var_matrix(int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data, c.ctypes.data,
-                                      None if v is None else v.ctypes.data, rowptr.ctypes.data, colidx.ctypes.data, val.ctypes.data,
-                                      nnz, C.byref(got)))
-    assert got.value == nnz == rowptr[-1]
-    return sp.csr_matrix((val[:nnz], colidx[:nnz], rowptr), shape=(n, n))
+    n, nnz = _grid_nnz(dims)
+    return _host_grid_csr(lib.ks_host_grid_var_matrix, n, nnz, dt, int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data,
+                          c.ctypes.data, None if v is None else v.ctypes.data)
 
 
 def host_operator(fn, n: int, dtype=np.float64, ctx: Context | None = None) -> Operator:

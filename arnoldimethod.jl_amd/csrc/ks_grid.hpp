@@ -1,67 +1,157 @@
-// Matrix-free grid operator  y = A x  for a constant-coefficient 3-, 5- or 7-point stencil plus a per-point diagonal term on an
-// nx x ny x nz grid (ks_operator_grid, include/kschur.h): mul!(y, A, x), src/expansion.jl:121, for A = -Laplacian + V(x) and its
-// kin, with NOTHING stored per non-zero.  The grid shape gives the boundary rows by index arithmetic, the seven taps travel in the
+// Matrix-free grid operators  y = A x  on an nx x ny x nz grid: mul!(y, A, x), src/expansion.jl:121, for A = -Laplacian + V(x) and
+// its kin, with NOTHING stored per non-zero.  The grid shape gives the boundary rows by index arithmetic, the taps travel in the
 // kernel arguments, the only per-row datum is the diagonal entry centre + potential[r] (formed once on the host at upload, by the
-// code that ks_host_grid_matrix runs).
+// code that the host matrix runs).  This file: what every grid kernel shares, then the constant-coefficient operators (k_grid: 3-, 5-
+// or 7-point stencil with open or periodic boundaries, ks_operator_grid / ks_operator_grid_periodic; k_grid_star: star stencils of
+// radius 2, 3, 4, ks_operator_grid_star).  ks_grid_var.hpp: the variable-coefficient operator (k_grid_var).
 // Part of the ONE translation unit of libkschur_hip.so: included by ks_hip.hip after ks_tridiag.hpp.
 //
-// The operator IS the matrix ks_host_grid_matrix returns: the kernel rounds every product on its own and adds the products of a row
-// to +0.0 in ascending column order (-z, -y, -x, centre, +x, +y, +z; a tap whose neighbour lies outside the grid is skipped), so y
-// carries the bits every stored layout of that matrix gives.
+// An operator IS the matrix its ks_host_grid_* entry returns: the kernel rounds every product on its own and adds the products of a
+// row to +0.0 in ascending column order (a tap whose neighbour lies outside the grid is skipped), so y carries the bits every stored
+// layout of that matrix gives.
 //
-// k_grid.  A workgroup of 256 threads owns an in-plane tile of TX x TY points (four points per thread) and walks up a range of
-// z-planes.  Per plane every thread keeps its own points of the planes z - 1, z, z + 1 in registers (the +-z taps never touch
-// memory a second time) and the planes z + 2 in flight; the points of plane z go into an LDS tile together with the tile's halo
-// (one cell per thread, loaded two planes ahead), from which the +-x and +-y taps are read.  Two LDS tiles alternate: one barrier
-// per plane.  The z-loop is unrolled by four so that the four register sets rotate by name: nothing waits for a load before the
-// step that uses it.  Compulsory traffic: x read once, the diagonal read once, y written once -- 24 bytes per row in Float64 (16 without
-// a potential), twice that in ComplexF64; on top of it the halo of a tile (2 (TX + TY) / (TX TY) of x: 12.5 % for 32 x 32) and
-// the two planes a z-range reads beyond its own, which neighbouring workgroups of the same XCD bring into its L2.
-// Every access is one element wide (8 bytes in Float64): a row starts at r = nx (...), for odd nx not 16-byte aligned, and nothing
-// here depends on it.
-// Tiles: 32 x 32 for grids with ny > 1, 1024 x 1 for ny == 1 (1-D grids, and nx x 1 x nz).  Work items are (z-range, tile), z-range
-// major, dealt to the XCDs in contiguous runs (xcd_remap) so that neighbouring tiles meet in one L2.
+// The scheme, for halo depth R (the stencil's radius).  A workgroup of 256 threads owns an in-plane tile of TX x TY points
+// (GridTile: four points per thread, or two) and walks up a range of z-planes.  Per plane every thread keeps its own points of the
+// planes z - R ... z + R in registers (the +-z taps never touch memory a second time) and a further plane in flight; the points of
+// plane z go into an LDS tile together with the tile's halo, R cells deep on each side (2 R (TX + TY) cells, dealt to the threads
+// and loaded two planes ahead; corners are never read), from which the +-x and +-y taps are read.  Two LDS tiles alternate: one
+// barrier per plane.  Work items are (z-range, tile), z-range major, dealt to the XCDs in contiguous runs (xcd_remap) so that
+// neighbouring tiles meet in one L2.  Every access is one element wide (8 bytes in Float64): a row starts at r = nx (...), for odd
+// nx not 16-byte aligned, and nothing here depends on it.
+// Compulsory traffic: x read once, the diagonal read once, y written once -- 24 bytes per row in Float64 (16 without a potential),
+// twice that in ComplexF64; on top of it the halo of a tile (R 2 (TX + TY) / (TX TY) of x: R x 12.5 % for 32 x 32) and the R planes
+// a z-range reads beyond each end, 2 R / zc of x, which neighbouring workgroups of the same XCD bring into its L2.  RULE for the
+// z-ranges (grid::plan): at least kGridMinZ * R = 8 R planes each, so that the plane re-read stays at most 25 %.
+// Every kernel argument `shifted`: bit 0 -- y = sigma (A x - theta x), the Newton step of the s-step expansion (as k_spmv_stencil2
+// stores it), bit 1 -- cacheable instead of streaming stores.  diag == nullptr: no potential, the diagonal entry is the centre tap.
+// st: a breakdown of the batch ends the kernel at once.
+// Shared by the three kernels, below: the geometry at the head of the arguments (GridGeom), the tiles (GridTile, GridLds), the
+// work-item decode (grid_item), the owned points and their neighbour flags (grid_owned, grid_neighbours), the diagonal load
+// (grid_ldd) and the end of a row (GridStore).  Written out in each kernel: the guarded plane load `ldx` and the assignment of halo
+// cells to threads -- as a function either one changes the order of the Float64 kernels' instructions (DESIGN).
 //
-// k_grid_star.  The star stencil of radius R = 2, 3, 4 (ks_operator_grid_star: central differences of order 4, 6, 8), open
-// boundaries, a kernel of its own so that k_grid is what it was.  Same scheme, R deep: every thread keeps its own points of the
-// 2 R + 1 planes z - R ... z + R in registers and plane z + R + 1 in flight, the LDS tile has a halo R cells deep on each side
-// (2 R (TX + TY) cells: up to two per thread), and the existence of the +-x / +-y taps of every distance d is one bit per tap in
-// one register per point, computed once per thread.  A row is summed in the 6 R + 1 slots -R z ... -1 z, -R y ... -1 y,
-// -R x ... -1 x, centre, +1 x ... +R x, +1 y ... +R y, +1 z ... +R z; an absent tap is not multiplied.
-// The 2 R + 2 register sets rotate by MOVES at the end of a plane, not by name: unrolled by 2 R + 2 the z-loop of R = 4 is 180 KB
-// of code and ran at 264 us per product on 216^3 against 111 us in this form (profiles/grid_operator.txt); the plane in flight
-// lands in a set of its own and is waited for after the plane's arithmetic.  The z-loop is unrolled by two (the LDS tiles, the
-// halo and the diagonal registers alternate).  The 4 R in-plane neighbours of a point are read from the tile before any of them
-// is used, and a wave all of whose lanes have the R taps of a direction -- every wave but those at an edge of the grid -- adds
-// them in straight-line code; only the other waves test tap by tap.
-// Traffic: the same 24 / 16 bytes per row; the halo re-read is R 2 (TX + TY) / (TX TY) of x (R x 12.5 % for 32 x 32) and a z-range
-// reads R planes beyond each end, 2 R / zc of x.  RULE for the z-ranges: at least kGridMinZ * R = 8 R planes each, so that the
-// plane re-read stays at most 25 % as at radius 1 (and the 2 R + 1 planes of the prologue are at most a quarter of the loads).
-// Tiles: Float64 32 x 32 and 1024 x 1 at every radius; ComplexF64 32 x 32 and 1024 x 1 at R = 2, 32 x 16 and 512 x 1 (two points
-// per thread) at R = 3 and 4, where four points of ten planes would take the kernel to one wave per SIMD (StarTile, DESIGN).
+// k_grid (R = 1).  Rows are summed in the slots -z, -y, -x, centre, +x, +y, +z.  Planes z - 1, z, z + 1 in registers and z + 2 in
+// flight; one halo cell per thread.  The z-loop is unrolled by four so that the four register sets rotate by name: nothing waits
+// for a load before the step that uses it.  Tiles: 32 x 32, and 1024 x 1 for ny == 1 (1-D grids, and nx x 1 x nz).
+//
+// k_grid_star (R = 2, 3, 4: central differences of order 4, 6, 8; open boundaries).  Up to two halo cells per thread, and the
+// existence of the +-x / +-y taps of every distance d is one bit per tap in one register per point, computed once per thread.  A
+// row is summed in the 6 R + 1 slots -R z ... -1 z, -R y ... -1 y, -R x ... -1 x, centre, +1 x ... +R x, +1 y ... +R y,
+// +1 z ... +R z; an absent tap is not multiplied.  The 2 R + 2 register sets rotate by MOVES at the end of a plane, not by name:
+// unrolled by 2 R + 2 the z-loop of R = 4 is 180 KB of code and ran at 264 us per product on 216^3 against 111 us in this form
+// (profiles/grid_operator.txt); the plane in flight lands in a set of its own and is waited for after the plane's arithmetic.  The
+// z-loop is unrolled by two (the LDS tiles, the halo and the diagonal registers alternate).  The 4 R in-plane neighbours of a point
+// are read from the tile before any of them is used, and a wave all of whose lanes have the R taps of a direction -- every wave
+// but those at an edge of the grid -- adds them in straight-line code; only the other waves test tap by tap.
+// Tiles: Float64 32 x 32 and 1024 x 1 at every radius; ComplexF64 the same at R = 2, 32 x 16 and 512 x 1 (two points per thread)
+// at R = 3 and 4, where four points of ten planes would take the kernel to one wave per SIMD (DESIGN).
 #pragma once
 
 namespace ksd {
 
-constexpr int kGridMinZ = 8;       // planes per z-range, at least: a range reads two planes beyond its own (radius R: 8 R, 2 R beyond)
+constexpr int kGridMinZ = 8;       // planes per z-range, at least, per unit of radius
 constexpr int kGridWant = 1024;    // work items per launch, at most, while z can be split: what an MI355X holds at once (4 per CU)
 
-template <class T> struct GridDev {
+// what every grid kernel's argument struct starts with
+struct GridGeom {
   int nx = 1, ny = 1, nz = 1;
   int ntx = 1, nty = 1;   // tiles along x and y
   int zc = 1;             // planes per z-range
+};
+// k_grid, k_grid_var (whose six off-diagonal slots hold the HALF taps)
+template <class T> struct GridDev : GridGeom {
   T tap[7] = {};          // -z, -y, -x, centre, +x, +y, +z
 };
-// ... with periodic axes (ks_operator_grid_periodic): the entries of the links that cross the cell boundary and the axes that wrap.
-// A type of its own, so that the open operator's kernel and its arguments are what they were.
+// ... with periodic axes: the entries of the links that cross the cell boundary and the axes that wrap
 template <class T> struct GridPerDev : GridDev<T> {
   T wrap[6] = {};         // -z, -y, -x, +x, +y, +z
   int px = 0, py = 0, pz = 0;
 };
+template <class T, int R> struct GridStarDev : GridGeom {
+  T tap[6 * R + 1] = {};  // -R z ... -1 z, -R y ... -1 y, -R x ... -1 x, centre, +1 x ... +R x, +1 y ... +R y, +1 z ... +R z
+};
+static_assert(sizeof(GridDev<double>) == 24 + 7 * 8 && sizeof(GridDev<cd>) == 24 + 7 * 16 && sizeof(GridStarDev<cd, 2>) == 24 + 13 * 16,
+              "kernel arguments: six ints, then the taps with nothing between");
 
-// shifted: bit 0 -- y = sigma (A x - theta x), the Newton step of the s-step expansion (as k_spmv_stencil2 stores it), bit 1 --
-// cacheable instead of streaming stores.  diag == nullptr: no potential, the diagonal entry is tap[3].
-//
+// The in-plane tiles: TX x TY for ny > 1, WX x 1 for ny == 1.  Four points per thread; two (HALF) where four would cost the second
+// wave per SIMD: ComplexF64 with the planes of R >= 3 or with a coefficient beside x in registers and LDS (DESIGN).
+template <bool HALF> struct GridTile {
+  static constexpr int TX = 32, TY = HALF ? 16 : 32;
+  static constexpr int WX = HALF ? 512 : 1024;
+};
+constexpr bool grid_half(size_t elem, int R, bool var) { return elem == 16 && (R >= 3 || var); }
+template <class T, int R = 1, bool VAR = false> using GridTileOf = GridTile<grid_half(sizeof(T), R, VAR)>;
+
+// the LDS tile of a TX x TY tile with its halo of depth R
+template <int TX, int TY, int R> struct GridLds {
+  static constexpr int PPT = TX * TY / kBlock;             // points per thread
+  static constexpr int HY = TY > 1 ? R : 0;                // halo rows in y on each side (a one-row tile: ny == 1, no y neighbours)
+  static constexpr int LW = TX + 2 * R, LH = TY + 2 * HY;  // extents
+  static constexpr int NHALO = 2 * R * TY + 2 * HY * TX;   // halo cells (corners are never read)
+  static constexpr int NH = (NHALO + kBlock - 1) / kBlock; // ... per thread, at most
+  static_assert(TX * TY % kBlock == 0 && R >= 1 && R <= 4 && NH <= 2, "whole points per thread, at most two halo cells");
+};
+
+// the work item of this workgroup: its tile's first point, its planes [za, zb), and the plane stride
+struct GridItem {
+  int x0, y0, za, zb;
+  int64_t P;
+};
+template <int TX, int TY> __device__ __forceinline__ GridItem grid_item(const GridGeom& g) {
+  const int ntiles = g.ntx * g.nty;
+  const int item = xcd_remap((int)blockIdx.x, (int)gridDim.x);
+  const int zr = item / ntiles, t2 = item - zr * ntiles;
+  const int tyi = t2 / g.ntx, txi = t2 - tyi * g.ntx;
+  const int za = zr * g.zc;
+  return {txi * TX, tyi * TY, za, min(g.nz, za + g.zc), (int64_t)g.nx * g.ny};
+}
+
+// owned point p of the tile (this thread's k-th: p = tid + k kBlock): grid coordinates, inside the grid, in-plane offset, place in
+// the LDS tile
+template <int TX, int TY, int R>
+__device__ __forceinline__ void grid_owned(const GridGeom& g, const GridItem& it, int p, int& gx, int& gy, bool& in, int64_t& off, int& li) {
+  using L = GridLds<TX, TY, R>;
+  const int lx = p % TX, ly = p / TX;
+  gx = it.x0 + lx;
+  gy = it.y0 + ly;
+  in = gx < g.nx && gy < g.ny;
+  off = (int64_t)gy * g.nx + gx;
+  li = (ly + L::HY) * L::LW + lx + R;
+}
+// ... has a -x / +x / -y / +y neighbour (R = 1)
+__device__ __forceinline__ void grid_neighbours(const GridGeom& g, const int& gx, const int& gy, const bool& in, bool& hxm, bool& hxp, bool& hym,
+                                                bool& hyp) {
+  hxm = in && gx > 0;
+  hxp = in && gx + 1 < g.nx;
+  hym = in && gy > 0;
+  hyp = in && gy + 1 < g.ny;
+}
+
+// Element o of plane z of the diagonal.  Like every load of these kernels: a point outside the grid or the planes is never loaded,
+// zero stands in and is never multiplied into a stored row.
+template <class T> __device__ __forceinline__ T grid_ldd(const T* diag, const GridGeom& g, int64_t P, int z, int64_t o, bool ok) {
+  return ok && z < g.nz ? ld_val(diag + ((int64_t)z * P + o), true) : zero_of(T{});
+}
+
+// the end of a row: the fused Newton step, then the store (cacheable or streaming) if the point lies inside the grid
+template <class T> struct GridStore {
+  T* const y;
+  const int64_t P;
+  const int shifted;
+  const T theta;
+  const double sigma;
+  const bool plain = (shifted & 2) != 0;
+  // s: the row's sum, xc: its own point, at offset o of plane z
+  __device__ __forceinline__ void operator()(int z, int64_t o, bool in, T s, const T& xc) const {
+    if (shifted & 1) s = scl(sub_s(s, mul_(theta, xc)), sigma);
+    if (in) {
+      T* dst = y + ((int64_t)z * P + o);
+      if (plain) *dst = s;
+      else st_elem_nt(dst, s);
+    }
+  }
+};
+
 // G = GridPerDev<T>: periodic axes.  A row is summed in the 13-slot order of include/kschur.h (ix), a wrap link at ANOTHER place than
 // the interior link of its direction: the column of a +wrap link lies below every other column of its axis, that of a -wrap link
 // above.  x and y: a halo cell one step outside the grid loads from the other end of its line.  When the last tile is partial the
@@ -74,20 +164,15 @@ __global__ void __launch_bounds__(kBlock)
            int shifted, T theta, double sigma) {
   if (st && st->breakdown >= 0) return;
   constexpr bool PER = !std::is_same<G, GridDev<T>>::value;
-  constexpr int PPT = TX * TY / kBlock;          // points per thread
-  constexpr int HY = TY > 1 ? 1 : 0;             // halo rows in y (a one-row tile belongs to a grid with ny == 1: no y neighbours)
-  constexpr int LW = TX + 2, LH = TY + 2 * HY;   // LDS tile with its halo
-  constexpr int NHALO = 2 * TY + 2 * HY * TX;    // halo cells (corners are never read)
-  static_assert(TX * TY % kBlock == 0 && NHALO <= kBlock, "four points and at most one halo cell per thread");
-  __shared__ T tile[2][LH * LW];
-  const int ntiles = g.ntx * g.nty;
-  const int item = xcd_remap((int)blockIdx.x, (int)gridDim.x);
-  const int zr = item / ntiles, t2 = item - zr * ntiles;
-  const int tyi = t2 / g.ntx, txi = t2 - tyi * g.ntx;
-  const int x0 = txi * TX, y0 = tyi * TY;
-  const int za = zr * g.zc, zb = min(g.nz, za + g.zc);
-  const int64_t P = (int64_t)g.nx * g.ny;
+  using L = GridLds<TX, TY, 1>;
+  constexpr int PPT = L::PPT, HY = L::HY, LW = L::LW;
+  static_assert(L::NH == 1, "at most one halo cell per thread");
+  __shared__ T tile[2][L::LH * LW];
+  const GridItem it = grid_item<TX, TY>(g);
+  const int za = it.za, zb = it.zb;
+  const int64_t P = it.P;
   const int tid = (int)threadIdx.x;
+  const GridStore<T> store{y, P, shifted, theta, sigma};
 
   int64_t off[PPT];   // in-plane offset of the owned points
   int li[PPT];        // ... and their place in the LDS tile
@@ -97,16 +182,9 @@ __global__ void __launch_bounds__(kBlock)
   int64_t loff[PPT];
 #pragma unroll
   for (int k = 0; k < PPT; ++k) {
-    const int p = tid + k * kBlock;
-    const int lx = p % TX, ly = p / TX;
-    const int gx = x0 + lx, gy = y0 + ly;
-    in[k] = gx < g.nx && gy < g.ny;
-    off[k] = (int64_t)gy * g.nx + gx;
-    li[k] = (ly + HY) * LW + lx + 1;
-    hxm[k] = in[k] && gx > 0;
-    hxp[k] = in[k] && gx + 1 < g.nx;
-    hym[k] = in[k] && gy > 0;
-    hyp[k] = in[k] && gy + 1 < g.ny;
+    int gx, gy;
+    grid_owned<TX, TY, 1>(g, it, tid + k * kBlock, gx, gy, in[k], off[k], li[k]);
+    grid_neighbours(g, gx, gy, in[k], hxm[k], hxp[k], hym[k], hyp[k]);
     if constexpr (PER) {
       wxm[k] = in[k] && g.px && gx == 0;
       wxp[k] = in[k] && g.px && gx + 1 == g.nx;
@@ -121,13 +199,13 @@ __global__ void __launch_bounds__(kBlock)
   bool hin = false;
   int64_t hoff = 0;
   int hli = 0;
-  if (tid < NHALO) {
+  if (tid < L::NHALO) {
     int hx, hy;
     if (tid < TY) { hx = -1; hy = tid; }
     else if (tid < 2 * TY) { hx = TX; hy = tid - TY; }
     else if (tid < 2 * TY + TX) { hx = tid - 2 * TY; hy = -1; }
     else { hx = tid - 2 * TY - TX; hy = TY; }
-    int gx = x0 + hx, gy = y0 + hy;
+    int gx = it.x0 + hx, gy = it.y0 + hy;
     if constexpr (PER) {
       if (g.px) gx = gx == -1 ? g.nx - 1 : gx == g.nx ? 0 : gx;
       if (g.py) gy = gy == -1 ? g.ny - 1 : gy == g.ny ? 0 : gy;
@@ -136,7 +214,6 @@ __global__ void __launch_bounds__(kBlock)
     hoff = (int64_t)gy * g.nx + gx;
     hli = (hy + HY) * LW + hx + 1;
   }
-  // (a point outside the grid or the planes is never loaded: zero stands in and is never multiplied into a stored row)
   auto ldx = [&](int z, int64_t o, bool ok) {
     if constexpr (PER) {
       if (g.pz) z = z < 0 ? g.nz - 1 : z >= g.nz ? 0 : z;   // (z is never further out than one plane)
@@ -148,7 +225,6 @@ __global__ void __launch_bounds__(kBlock)
     if constexpr (PER) return ldx(z, loff[k], ldk[k] && ok);
     else return ldx(z, off[k], in[k] && ok);
   };
-  auto ldd = [&](int z, int64_t o, bool ok) { return ok && z < g.nz ? ld_val(diag + ((int64_t)z * P + o), true) : zero_of(T{}); };
 
   // Register sets: xr[0..3] hold the owned points of four consecutive planes and rotate by NAME, not by moves (the z-loop is
   // unrolled by four): a load issued in one step lands in the set that step no longer needs and is first read one barrier and
@@ -161,21 +237,20 @@ __global__ void __launch_bounds__(kBlock)
     xr[0][k] = ldo(za - 1, k, true);
     xr[1][k] = ldo(za, k, true);
     xr[2][k] = ldo(za + 1, k, true);
-    dr[0][k] = diag ? ldd(za, off[k], in[k]) : g.tap[3];
+    dr[0][k] = diag ? grid_ldd(diag, g, P, za, off[k], in[k]) : g.tap[3];
     dr[1][k] = dr[0][k];
   }
-  const bool plain_st = (shifted & 2) != 0;
   // one plane: xm / xc / xp = planes z - 1 / z / z + 1, xn receives plane z + 2; hw = the halo cell of plane z, then of z + 2
   auto step = [&](int z, const T (&xm)[PPT], const T (&xc)[PPT], const T (&xp)[PPT], T (&xn)[PPT], T& hw, const T (&dc)[PPT], T (&dn)[PPT],
                   T* __restrict__ tl) {
 #pragma unroll
     for (int k = 0; k < PPT; ++k) tl[li[k]] = xc[k];
-    if (tid < NHALO) tl[hli] = hw;
+    if (tid < L::NHALO) tl[hli] = hw;
     hw = ldx(z + 2, hoff, hin && z + 2 < zb);
 #pragma unroll
     for (int k = 0; k < PPT; ++k) {
       xn[k] = ldo(z + 2, k, z + 2 <= zb);   // (plane zb is the +z tap of the range's last plane)
-      if (diag) dn[k] = ldd(z + 1, off[k], in[k] && z + 1 < zb);
+      if (diag) dn[k] = grid_ldd(diag, g, P, z + 1, off[k], in[k] && z + 1 < zb);
     }
     __syncthreads();
 #pragma unroll
@@ -210,12 +285,7 @@ __global__ void __launch_bounds__(kBlock)
       if constexpr (PER) {
         if (g.pz && z == 0) s = add_(s, mul_nc(g.wrap[0], xm[k]));
       }
-      if (shifted & 1) s = scl(sub_s(s, mul_(theta, xc[k])), sigma);
-      if (in[k]) {
-        T* dst = y + ((int64_t)z * P + off[k]);
-        if (plain_st) *dst = s;
-        else st_elem_nt(dst, s);
-      }
+      store(z, off[k], in[k], s, xc[k]);
     }
   };
   // (the exits are uniform over the workgroup: the barriers match)
@@ -231,19 +301,6 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 // ---------------------------------------------------------------------------------------------- radius 2, 3, 4 (open boundaries)
-template <class T, int R> struct GridStarDev {
-  int nx = 1, ny = 1, nz = 1;
-  int ntx = 1, nty = 1;   // tiles along x and y
-  int zc = 1;             // planes per z-range
-  T tap[6 * R + 1] = {};  // -R z ... -1 z, -R y ... -1 y, -R x ... -1 x, centre, +1 x ... +R x, +1 y ... +R y, +1 z ... +R z
-};
-// the in-plane tile of k_grid_star: four points per thread, two where four would cost the second wave per SIMD (ComplexF64, R >= 3)
-template <class T, int R> struct StarTile {
-  static constexpr bool kHalf = sizeof(T) == 16 && R >= 3;
-  static constexpr int TX = 32, TY = kHalf ? 16 : 32;   // ny > 1
-  static constexpr int WX = kHalf ? 512 : 1024;         // ny == 1: WX x 1
-};
-
 // steps J, J + 1, ..., N - 1 of one turn of the unrolled z-loop, each with its number as a compile-time constant (its parity
 // picks the LDS tile and the halo and diagonal registers); stops after the range's last plane (uniform over the workgroup: the
 // barriers match)
@@ -254,28 +311,21 @@ template <int J, int N, class F> __device__ __forceinline__ void grid_star_steps
   }
 }
 
-// shifted, diag: as k_grid.
 template <class T, int TX, int TY, int R>
 __global__ void __launch_bounds__(kBlock)
     k_grid_star(const GridStarDev<T, R> g, const T* __restrict__ x, const T* __restrict__ diag, T* __restrict__ y,
                 const DevState* __restrict__ st, int shifted, T theta, double sigma) {
   if (st && st->breakdown >= 0) return;
-  constexpr int PPT = TX * TY / kBlock;                  // points per thread
-  constexpr int HY = TY > 1 ? R : 0;                     // halo rows in y on each side (a one-row tile: ny == 1, no y neighbours)
-  constexpr int LW = TX + 2 * R, LH = TY + 2 * HY;       // LDS tile with its halo
-  constexpr int NHALO = 2 * R * TY + 2 * HY * TX;        // halo cells (corners are never read)
-  constexpr int NH = (NHALO + kBlock - 1) / kBlock;      // ... per thread, at most
+  using L = GridLds<TX, TY, R>;
+  constexpr int PPT = L::PPT, HY = L::HY, LW = L::LW, NH = L::NH;
   constexpr int N = 2 * R + 2;                           // register sets: planes z - R ... z + R and the one in flight
-  static_assert(TX * TY % kBlock == 0 && R >= 2 && R <= 4 && NH <= 2, "whole points per thread, at most two halo cells");
-  __shared__ T tile[2][LH * LW];
-  const int ntiles = g.ntx * g.nty;
-  const int item = xcd_remap((int)blockIdx.x, (int)gridDim.x);
-  const int zr = item / ntiles, t2 = item - zr * ntiles;
-  const int tyi = t2 / g.ntx, txi = t2 - tyi * g.ntx;
-  const int x0 = txi * TX, y0 = tyi * TY;
-  const int za = zr * g.zc, zb = min(g.nz, za + g.zc);
-  const int64_t P = (int64_t)g.nx * g.ny;
+  static_assert(R >= 2, "radius 1 is k_grid");
+  __shared__ T tile[2][L::LH * LW];
+  const GridItem it = grid_item<TX, TY>(g);
+  const int za = it.za, zb = it.zb;
+  const int64_t P = it.P;
   const int tid = (int)threadIdx.x;
+  const GridStore<T> store{y, P, shifted, theta, sigma};
 
   int64_t off[PPT];   // in-plane offset of the owned points
   int li[PPT];        // ... and their place in the LDS tile
@@ -283,12 +333,8 @@ __global__ void __launch_bounds__(kBlock)
   unsigned msk[PPT];  // bit d - 1 / 4 + d - 1 / 8 + d - 1 / 12 + d - 1: has a neighbour at -d x / +d x / -d y / +d y
 #pragma unroll
   for (int k = 0; k < PPT; ++k) {
-    const int p = tid + k * kBlock;
-    const int lx = p % TX, ly = p / TX;
-    const int gx = x0 + lx, gy = y0 + ly;
-    in[k] = gx < g.nx && gy < g.ny;
-    off[k] = (int64_t)gy * g.nx + gx;
-    li[k] = (ly + HY) * LW + lx + R;
+    int gx, gy;
+    grid_owned<TX, TY, R>(g, it, tid + k * kBlock, gx, gy, in[k], off[k], li[k]);
     msk[k] = 0u;
 #pragma unroll
     for (int d = 1; d <= R; ++d) {
@@ -311,21 +357,19 @@ __global__ void __launch_bounds__(kBlock)
     hin[j] = false;
     hoff[j] = 0;
     hli[j] = 0;
-    if (c < NHALO) {
+    if (c < L::NHALO) {
       int hx, hy;
       if (c < R * TY) { hx = -1 - c / TY; hy = c % TY; }
       else if (c < 2 * R * TY) { hx = TX + (c - R * TY) / TY; hy = (c - R * TY) % TY; }
       else if (c < 2 * R * TY + R * TX) { hx = (c - 2 * R * TY) % TX; hy = -1 - (c - 2 * R * TY) / TX; }
       else { hx = (c - 2 * R * TY - R * TX) % TX; hy = TY + (c - 2 * R * TY - R * TX) / TX; }
-      const int gx = x0 + hx, gy = y0 + hy;
+      const int gx = it.x0 + hx, gy = it.y0 + hy;
       hin[j] = gx >= 0 && gx < g.nx && gy >= 0 && gy < g.ny;
       hoff[j] = (int64_t)gy * g.nx + gx;
       hli[j] = (hy + HY) * LW + hx + R;
     }
   }
-  // (a point outside the grid or the planes is never loaded: zero stands in and is never multiplied into a stored row)
   auto ldx = [&](int z, int64_t o, bool ok) { return ok && z >= 0 && z < g.nz ? x[(int64_t)z * P + o] : zero_of(T{}); };
-  auto ldd = [&](int z, int64_t o, bool ok) { return ok && z < g.nz ? ld_val(diag + ((int64_t)z * P + o), true) : zero_of(T{}); };
 
   // Register sets: at plane z set R + d holds the owned points of plane z + d, d = -R ... R, and set N - 1 receives plane
   // z + R + 1; after the plane's arithmetic every set moves down by one.  hr[0..1]: the halo cells of the planes of even / odd
@@ -341,10 +385,9 @@ __global__ void __launch_bounds__(kBlock)
 #pragma unroll
     for (int s = 0; s <= 2 * R; ++s) xr[s][k] = ldx(za - R + s, off[k], in[k]);
     xr[N - 1][k] = zero_of(T{});
-    dr[0][k] = diag ? ldd(za, off[k], in[k]) : g.tap[3 * R];
+    dr[0][k] = diag ? grid_ldd(diag, g, P, za, off[k], in[k]) : g.tap[3 * R];
     dr[1][k] = dr[0][k];
   }
-  const bool plain_st = (shifted & 2) != 0;
   // The R taps of one direction, added to s in slot order: the tap of distance d is g.tap[BASE + SGN d], its neighbour v[d - 1],
   // and it exists where bit d - 1 of gm is set; SGN = -1: d = R ... 1, SGN = +1: d = 1 ... R.  Where every lane of the wave has
   // all R taps -- every wave but those at an edge of the grid -- the sum is straight-line code; elsewhere each tap is
@@ -376,13 +419,13 @@ __global__ void __launch_bounds__(kBlock)
     for (int k = 0; k < PPT; ++k) tl[li[k]] = xc[k];
 #pragma unroll
     for (int j = 0; j < NH; ++j) {
-      if (tid + j * kBlock < NHALO) tl[hli[j]] = hr[B][j];
+      if (tid + j * kBlock < L::NHALO) tl[hli[j]] = hr[B][j];
       hr[B][j] = ldx(z + 2, hoff[j], hin[j] && z + 2 < zb);
     }
 #pragma unroll
     for (int k = 0; k < PPT; ++k) {
       xn[k] = ldx(z + R + 1, off[k], in[k] && z + 1 < zb);   // (the +R z tap of the next plane; beyond zb for the range's last R)
-      if (diag) dr[1 - B][k] = ldd(z + 1, off[k], in[k] && z + 1 < zb);
+      if (diag) dr[1 - B][k] = grid_ldd(diag, g, P, z + 1, off[k], in[k] && z + 1 < zb);
     }
     __syncthreads();
     // the z taps as masks of the same kind (uniform): -d z exists for d <= z, +d z for d <= nz - 1 - z
@@ -420,12 +463,7 @@ __global__ void __launch_bounds__(kBlock)
       s = grp(s, m >> 4, std::integral_constant<int, 3 * R>{}, Q{}, vxp);
       if constexpr (HY > 0) s = grp(s, m >> 12, std::integral_constant<int, 4 * R>{}, Q{}, vyp);
       s = grp(s, zmp, std::integral_constant<int, 5 * R>{}, Q{}, vzp);
-      if (shifted & 1) s = scl(sub_s(s, mul_(theta, xc[k])), sigma);
-      if (in[k]) {
-        T* dst = y + ((int64_t)z * P + off[k]);
-        if (plain_st) *dst = s;
-        else st_elem_nt(dst, s);
-      }
+      store(z, off[k], in[k], s, xc[k]);
     }
 #pragma unroll
     for (int k = 0; k < PPT; ++k) {
@@ -525,43 +563,6 @@ template <class H> void seven_taps(int ndim, const H* t, H (&out)[7]) {
   for (H& o : out) o = H(0);
   for (int k = 0; k < 2 * ndim + 1; ++k) out[3 - ndim + k] = t[k];
 }
-
-// The matrix the operator is defined by, as 0-based CSR with ascending columns.  rowptr is always filled; colidx / val only when
-// cap >= nnz.  With periodic axes a row is a sub-sequence of the 13 slots of include/kschur.h (ix): the link of the last point of a
-// line to the first has the lowest column of its axis, that of the first to the last the highest.
-template <class H>
-void host_matrix(const std::string& who, const Shape& s, int ndim, const H* taps, const H* pot, const Wrap<H>& W, int64_t* rowptr,
-                 int32_t* colidx, H* val, int64_t cap, int64_t* nnz) {
-  if (nnz) *nnz = s.nnz;
-  KS_REQUIRE(cap >= s.nnz, KS_ERR_ARGUMENT,
-             who + ": cap = " + std::to_string(cap) + " is too small, the matrix has " + std::to_string(s.nnz) + " entries");
-  KS_REQUIRE(rowptr && (s.nnz == 0 || (colidx && val)), KS_ERR_ARGUMENT, who + ": null output array");
-  H t[7];
-  seven_taps(ndim, taps, t);
-  const int64_t P = s.nx * s.ny;
-  int64_t q = 0, r = 0;
-  for (int64_t iz = 0; iz < s.nz; ++iz)
-    for (int64_t iy = 0; iy < s.ny; ++iy)
-      for (int64_t ix = 0; ix < s.nx; ++ix, ++r) {
-        rowptr[r] = q;
-        auto put = [&](int64_t c, const H& v) { colidx[q] = (int32_t)c; val[q] = v; ++q; };
-        if (W.per[2] && iz + 1 == s.nz) put(r - (s.nz - 1) * P, W.w[5]);
-        if (iz > 0) put(r - P, t[0]);
-        if (W.per[1] && iy + 1 == s.ny) put(r - (s.ny - 1) * s.nx, W.w[4]);
-        if (iy > 0) put(r - s.nx, t[1]);
-        if (W.per[0] && ix + 1 == s.nx) put(r - (s.nx - 1), W.w[3]);
-        if (ix > 0) put(r - 1, t[2]);
-        put(r, pot ? diag_add(t[3], pot[r]) : t[3]);
-        if (ix + 1 < s.nx) put(r + 1, t[4]);
-        if (W.per[0] && ix == 0) put(r + (s.nx - 1), W.w[2]);
-        if (iy + 1 < s.ny) put(r + s.nx, t[5]);
-        if (W.per[1] && iy == 0) put(r + (s.ny - 1) * s.nx, W.w[1]);
-        if (iz + 1 < s.nz) put(r + P, t[6]);
-        if (W.per[2] && iz == 0) put(r + (s.nz - 1) * P, W.w[0]);
-      }
-  rowptr[s.n] = q;
-}
-
 // the 2 ndim R + 1 taps of a star stencil in the 6 R + 1 slots -R z ... -1 z, -R y ... -1 y, -R x ... -1 x, centre, +1 x ... +R x,
 // +1 y ... +R y, +1 z ... +R z (slots of a missing dimension: zero, never used)
 template <class H> void star_taps(int ndim, int R, const H* t, H (&out)[25]) {
@@ -569,15 +570,63 @@ template <class H> void star_taps(int ndim, int R, const H* t, H (&out)[25]) {
   for (int k = 0; k < 2 * ndim * R + 1; ++k) out[(3 - ndim) * R + k] = t[k];
 }
 
+// Every host matrix: 0-based CSR with ascending columns, the diagonal entry centre + potential[r] stored even where it is zero.
+// nnz is always reported; the arrays are filled only when cap >= nnz.
+template <class H>
+void csr_begin(const std::string& who, const Shape& s, const int64_t* rowptr, const int32_t* colidx, const H* val, int64_t cap, int64_t* nnz) {
+  if (nnz) *nnz = s.nnz;
+  KS_REQUIRE(cap >= s.nnz, KS_ERR_ARGUMENT,
+             who + ": cap = " + std::to_string(cap) + " is too small, the matrix has " + std::to_string(s.nnz) + " entries");
+  KS_REQUIRE(rowptr && (s.nnz == 0 || (colidx && val)), KS_ERR_ARGUMENT, who + ": null output array");
+}
+
+// The rows of a radius-1 matrix.  link(k, r, c, wrapped) is the entry of the link from row r to column c in tap slot k; on a
+// periodic axis (per: x, y, z) a row is a sub-sequence of the 13 slots of include/kschur.h (ix): the link of the last point of a
+// line to the first (wrapped) has the lowest column of its axis, that of the first to the last the highest.
+template <class H, class F>
+void seven_slot_rows(const Shape& s, const bool (&per)[3], const H& centre, const H* pot, int64_t* rowptr, int32_t* colidx, H* val, F link) {
+  const int64_t P = s.nx * s.ny;
+  int64_t q = 0, r = 0;
+  for (int64_t iz = 0; iz < s.nz; ++iz)
+    for (int64_t iy = 0; iy < s.ny; ++iy)
+      for (int64_t ix = 0; ix < s.nx; ++ix, ++r) {
+        rowptr[r] = q;
+        auto put = [&](int64_t c, const H& v) { colidx[q] = (int32_t)c; val[q] = v; ++q; };
+        auto to = [&](int k, int64_t c, bool wrapped) { put(c, link(k, r, c, wrapped)); };
+        if (per[2] && iz + 1 == s.nz) to(6, r - (s.nz - 1) * P, true);
+        if (iz > 0) to(0, r - P, false);
+        if (per[1] && iy + 1 == s.ny) to(5, r - (s.ny - 1) * s.nx, true);
+        if (iy > 0) to(1, r - s.nx, false);
+        if (per[0] && ix + 1 == s.nx) to(4, r - (s.nx - 1), true);
+        if (ix > 0) to(2, r - 1, false);
+        put(r, pot ? diag_add(centre, pot[r]) : centre);
+        if (ix + 1 < s.nx) to(4, r + 1, false);
+        if (per[0] && ix == 0) to(2, r + (s.nx - 1), true);
+        if (iy + 1 < s.ny) to(5, r + s.nx, false);
+        if (per[1] && iy == 0) to(1, r + (s.ny - 1) * s.nx, true);
+        if (iz + 1 < s.nz) to(6, r + P, false);
+        if (per[2] && iz == 0) to(0, r + (s.nz - 1) * P, true);
+      }
+  rowptr[s.n] = q;
+}
+
+// the matrix of ks_host_grid_matrix and ks_host_grid_matrix_periodic: the taps, and the wrap values for the links that cross
+template <class H>
+void host_matrix(const std::string& who, const Shape& s, int ndim, const H* taps, const H* pot, const Wrap<H>& W, int64_t* rowptr,
+                 int32_t* colidx, H* val, int64_t cap, int64_t* nnz) {
+  csr_begin(who, s, rowptr, colidx, val, cap, nnz);
+  H t[7];
+  seven_taps(ndim, taps, t);
+  seven_slot_rows(s, W.per, t[3], pot, rowptr, colidx, val,
+                  [&](int k, int64_t, int64_t, bool wrapped) { return wrapped ? W.w[k - (k > 3)] : t[k]; });
+}
+
 // The matrix that defines the star operator of radius R (ks_host_grid_matrix_star, include/kschur.h (x)): open boundaries, a row is
 // a sub-sequence of the 6 R + 1 slots.
 template <class H>
 void host_matrix_star(const std::string& who, const Shape& s, int ndim, int R, const H* taps, const H* pot, int64_t* rowptr,
                       int32_t* colidx, H* val, int64_t cap, int64_t* nnz) {
-  if (nnz) *nnz = s.nnz;
-  KS_REQUIRE(cap >= s.nnz, KS_ERR_ARGUMENT,
-             who + ": cap = " + std::to_string(cap) + " is too small, the matrix has " + std::to_string(s.nnz) + " entries");
-  KS_REQUIRE(rowptr && (s.nnz == 0 || (colidx && val)), KS_ERR_ARGUMENT, who + ": null output array");
+  csr_begin(who, s, rowptr, colidx, val, cap, nnz);
   H t[25];
   star_taps(ndim, R, taps, t);
   const int64_t P = s.nx * s.ny;
@@ -618,43 +667,76 @@ void host_matrix_star_entry(const std::string& who, int ndim, const int64_t* dim
     host_matrix_star<H>(who, s, ndim, radius, static_cast<const H*>(taps), static_cast<const H*>(pot), rowptr, colidx, static_cast<H*>(val), cap, nnz);
 }
 
+// the tile the kernels of an operator are launched with (ksd::GridTile; var: with a coefficient)
+struct Tile {
+  int64_t tx, ty;
+};
+template <class D> Tile tile(const Shape& s, int radius, bool var) {
+  auto of = [&](auto tl) { return s.ny == 1 ? Tile{decltype(tl)::WX, 1} : Tile{decltype(tl)::TX, decltype(tl)::TY}; };
+  return ksd::grid_half(sizeof(D), radius, var) ? of(ksd::GridTile<true>{}) : of(ksd::GridTile<false>{});
+}
+// The launch shape: the tiles along x and y, and the z-ranges -- as many as fill kGridWant work items, of at least
+// kGridMinZ * radius planes each.
+struct Plan {
+  ksd::GridGeom g;
+  int nitems = 0;   // workgroups of a launch
+};
+inline Plan plan(const std::string& who, const Shape& s, Tile tile, int radius) {
+  Plan p;
+  p.g.nx = (int)s.nx; p.g.ny = (int)s.ny; p.g.nz = (int)s.nz;
+  p.g.ntx = (int)((s.nx + tile.tx - 1) / tile.tx);
+  p.g.nty = (int)((s.ny + tile.ty - 1) / tile.ty);
+  const int64_t tiles = (int64_t)p.g.ntx * p.g.nty;
+  const int64_t ranges = std::max<int64_t>(1, ksd::kGridWant / tiles);
+  p.g.zc = (int)std::max<int64_t>(ksd::kGridMinZ * radius, (s.nz + ranges - 1) / ranges);
+  const int64_t items = tiles * ((s.nz + p.g.zc - 1) / p.g.zc);
+  KS_REQUIRE(items < (int64_t)2147483647, KS_ERR_ARGUMENT, who + ": too many tiles for one launch");
+  p.nitems = (int)items;
+  return p;
+}
+
 }  // namespace grid
 
-template <class D> struct GridOp : ks_operator {
-  ksd::GridPerDev<D> g{};   // (the open operator's kernel takes its GridDev part)
-  bool periodic = false;  // some axis wraps: the kernel's periodic instantiation
+// What the grid operators share: the diagonal, the launch shape, and the two products around the kernel launch of the subclass.
+template <class D> struct GridOpBase : ks_operator {
+  using H = typename HostT<D>::type;
+  static_assert(sizeof(H) == sizeof(D), "element layout");
   D* diag = nullptr;   // centre + potential[r] (null: no potential)
   int nitems = 0;      // workgroups of a launch
-  bool wide = false;   // the 1024 x 1 tile (ny == 1)
-  int radius = 1;      // > 1: the star stencil, k_grid_star with the taps of `star`
-  D star[25] = {};     // its 6 radius + 1 slots
+  bool wide = false;   // the one-row tile (ny == 1)
   double bytes = 0.0;  // algorithmic bytes of one product
-  ~GridOp() override { (void)hipFree(diag); }
-  void launch(const void* xv, void* yv, const DevState* st, int shifted, D theta, double sigma) {
-    KS_REQUIRE(xv != yv, KS_ERR_ARGUMENT, "grid operator: the product needs distinct x and y");
+  ~GridOpBase() override { (void)hipFree(diag); }
+  virtual void launch(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma) = 0;
+
+  // ctx, sizes, element type and the launch shape (geometry into g)
+  void init(ks_ctx* c, const std::string& who, const grid::Shape& s, int radius, bool var, ksd::GridGeom& g) {
+    ctx = c;
+    n_local = s.n;
+    nnz = s.nnz;
+    dtype = sizeof(D) == 8 ? KS_F64 : KS_C64;
+    const grid::Plan p = grid::plan(who, s, grid::tile<D>(s, radius, var), radius);
+    g = p.g;
+    nitems = p.nitems;
+    wide = s.ny == 1;
+  }
+  // the diagonal centre + potential[r] (none without a potential), and the bytes of a product: x, y and the diagonal
+  void upload_diag(const H& centre, const void* potential) {
+    if (potential) {
+      const H* v = static_cast<const H*>(potential);
+      std::vector<H> d((size_t)n_local);
+      for (int64_t r = 0; r < n_local; ++r) d[r] = grid::diag_add(centre, v[r]);
+      KS_HIP(hipMalloc(&diag, (size_t)n_local * sizeof(D)));
+      KS_HIP(hipMemcpy(diag, d.data(), (size_t)n_local * sizeof(D), hipMemcpyHostToDevice));
+    }
+    bytes = (double)n_local * sizeof(D) * (potential ? 3.0 : 2.0);
+  }
+  void product(const void* x, void* y, const DevState* st, int shifted, D theta, double sigma) {
+    KS_REQUIRE(x != y, KS_ERR_ARGUMENT, "grid operator: the product needs distinct x and y");
     ProfScope ps(ctx, KSP_SPMV, bytes);
-    const D* x = static_cast<const D*>(xv);
-    D* y = static_cast<D*>(yv);
-    const ksd::GridDev<D>& go = g;
-    if (radius == 2) launch_star<2>(x, y, st, shifted, theta, sigma);
-    else if (radius == 3) launch_star<3>(x, y, st, shifted, theta, sigma);
-    else if (radius == 4) launch_star<4>(x, y, st, shifted, theta, sigma);
-    else if (periodic) {
-      if (wide) ksd::k_grid<D, 1024, 1, ksd::GridPerDev<D>><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma);
-      else ksd::k_grid<D, 32, 32, ksd::GridPerDev<D>><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma);
-    } else if (wide) ksd::k_grid<D, 1024, 1, ksd::GridDev<D>><<<nitems, kBlock, 0, ctx->stream>>>(go, x, diag, y, st, shifted, theta, sigma);
-    else ksd::k_grid<D, 32, 32, ksd::GridDev<D>><<<nitems, kBlock, 0, ctx->stream>>>(go, x, diag, y, st, shifted, theta, sigma);
+    launch(static_cast<const D*>(x), static_cast<D*>(y), st, shifted, theta, sigma);
     KS_HIP(hipGetLastError());
   }
-  template <int R> void launch_star(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma) {
-    using TL = ksd::StarTile<D, R>;
-    ksd::GridStarDev<D, R> gs;
-    gs.nx = g.nx; gs.ny = g.ny; gs.nz = g.nz; gs.ntx = g.ntx; gs.nty = g.nty; gs.zc = g.zc;
-    for (int k = 0; k < 6 * R + 1; ++k) gs.tap[k] = star[k];
-    if (wide) ksd::k_grid_star<D, TL::WX, 1, R><<<nitems, kBlock, 0, ctx->stream>>>(gs, x, diag, y, st, shifted, theta, sigma);
-    else ksd::k_grid_star<D, TL::TX, TL::TY, R><<<nitems, kBlock, 0, ctx->stream>>>(gs, x, diag, y, st, shifted, theta, sigma);
-  }
-  void apply(const void* x, void* y, const DevState* st) override { launch(x, y, st, 0, D{}, 1.0); }
+  void apply(const void* x, void* y, const DevState* st) override { product(x, y, st, 0, D{}, 1.0); }
   // the Newton step in the same launch (KS_SHIFT_FUSED=0: the product and a streaming pass, like the stored layouts)
   void apply_shifted(const void* x, void* y, double tre, double tim, double sigma, int64_t ld, const DevState* st) override {
     if (!env_int("KS_SHIFT_FUSED", 1)) { ks_operator::apply_shifted(x, y, tre, tim, sigma, ld, st); return; }
@@ -662,7 +744,35 @@ template <class D> struct GridOp : ks_operator {
     const bool plain = env >= 0 ? env != 0 : shift_store_cacheable;
     D theta;
     if constexpr (sizeof(D) == 8) theta = tre; else theta = D{tre, tim};
-    launch(x, y, st, 1 | (plain ? 2 : 0), theta, sigma);
+    product(x, y, st, 1 | (plain ? 2 : 0), theta, sigma);
+  }
+};
+
+template <class D> struct GridOp : GridOpBase<D> {
+  using GridOpBase<D>::ctx; using GridOpBase<D>::diag; using GridOpBase<D>::nitems; using GridOpBase<D>::wide;
+  ksd::GridPerDev<D> g{};   // (the open operator's kernel takes its GridDev part)
+  bool periodic = false;  // some axis wraps: the kernel's periodic instantiation
+  int radius = 1;      // > 1: the star stencil, k_grid_star with the taps of `star`
+  D star[25] = {};     // its 6 radius + 1 slots
+  void launch(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma) override {
+    using TL = ksd::GridTileOf<D>;
+    const ksd::GridDev<D>& go = g;
+    if (radius == 2) launch_star<2>(x, y, st, shifted, theta, sigma);
+    else if (radius == 3) launch_star<3>(x, y, st, shifted, theta, sigma);
+    else if (radius == 4) launch_star<4>(x, y, st, shifted, theta, sigma);
+    else if (periodic) {
+      if (wide) ksd::k_grid<D, TL::WX, 1, ksd::GridPerDev<D>><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma);
+      else ksd::k_grid<D, TL::TX, TL::TY, ksd::GridPerDev<D>><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma);
+    } else if (wide) ksd::k_grid<D, TL::WX, 1, ksd::GridDev<D>><<<nitems, kBlock, 0, ctx->stream>>>(go, x, diag, y, st, shifted, theta, sigma);
+    else ksd::k_grid<D, TL::TX, TL::TY, ksd::GridDev<D>><<<nitems, kBlock, 0, ctx->stream>>>(go, x, diag, y, st, shifted, theta, sigma);
+  }
+  template <int R> void launch_star(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma) {
+    using TL = ksd::GridTileOf<D, R>;
+    ksd::GridStarDev<D, R> gs;
+    static_cast<ksd::GridGeom&>(gs) = g;
+    for (int k = 0; k < 6 * R + 1; ++k) gs.tap[k] = star[k];
+    if (wide) ksd::k_grid_star<D, TL::WX, 1, R><<<nitems, kBlock, 0, ctx->stream>>>(gs, x, diag, y, st, shifted, theta, sigma);
+    else ksd::k_grid_star<D, TL::TX, TL::TY, R><<<nitems, kBlock, 0, ctx->stream>>>(gs, x, diag, y, st, shifted, theta, sigma);
   }
 };
 
@@ -674,11 +784,6 @@ ks_operator* make_grid(ks_ctx* ctx, const std::string& who, int ndim, const int6
   KS_REQUIRE(radius == 1 || !periodic, KS_ERR_ARGUMENT, who + ": periodic axes take radius 1");
   const grid::Wrap<H> W = grid::check_wrap<H>(who, s, ndim, taps, periodic, wrap);
   auto op = std::make_unique<GridOp<D>>();
-  op->ctx = ctx;
-  op->n_local = s.n;
-  op->nnz = s.nnz;
-  op->dtype = sizeof(D) == 8 ? KS_F64 : KS_C64;
-  static_assert(sizeof(H) == sizeof(D), "element layout");
   H t[7], centre;
   if (radius == 1) {
     grid::seven_taps(ndim, static_cast<const H*>(taps), t);
@@ -694,26 +799,8 @@ ks_operator* make_grid(ks_ctx* ctx, const std::string& who, int ndim, const int6
   std::memcpy(op->g.wrap, W.w, sizeof(W.w));
   op->g.px = W.per[0]; op->g.py = W.per[1]; op->g.pz = W.per[2];
   op->periodic = W.any();
-  op->g.nx = (int)s.nx; op->g.ny = (int)s.ny; op->g.nz = (int)s.nz;
-  op->wide = s.ny == 1;
-  const bool half = radius > 1 && (radius == 2 ? ksd::StarTile<D, 2>::kHalf : radius == 3 ? ksd::StarTile<D, 3>::kHalf : ksd::StarTile<D, 4>::kHalf);
-  const int64_t tx = op->wide ? (half ? 512 : 1024) : 32, ty = op->wide ? 1 : half ? 16 : 32;
-  op->g.ntx = (int)((s.nx + tx - 1) / tx);
-  op->g.nty = (int)((s.ny + ty - 1) / ty);
-  const int64_t tiles = (int64_t)op->g.ntx * op->g.nty;
-  const int64_t ranges = std::max<int64_t>(1, ksd::kGridWant / tiles);
-  op->g.zc = (int)std::max<int64_t>(ksd::kGridMinZ * radius, (s.nz + ranges - 1) / ranges);
-  const int64_t items = tiles * ((s.nz + op->g.zc - 1) / op->g.zc);
-  KS_REQUIRE(items < (int64_t)2147483647, KS_ERR_ARGUMENT, who + ": too many tiles for one launch");
-  op->nitems = (int)items;
-  if (potential) {
-    const H* v = static_cast<const H*>(potential);
-    std::vector<H> d((size_t)s.n);
-    for (int64_t r = 0; r < s.n; ++r) d[r] = grid::diag_add(centre, v[r]);
-    KS_HIP(hipMalloc(&op->diag, (size_t)s.n * sizeof(D)));
-    KS_HIP(hipMemcpy(op->diag, d.data(), (size_t)s.n * sizeof(D), hipMemcpyHostToDevice));
-  }
-  op->bytes = (double)s.n * sizeof(D) * (potential ? 3.0 : 2.0);
+  op->init(ctx, who, s, radius, false, op->g);
+  op->upload_diag(centre, potential);
   return op.release();
 }
 

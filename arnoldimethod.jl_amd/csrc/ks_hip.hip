@@ -48,6 +48,30 @@ using ksd::kBlock;
 #include "ks_backend.hpp"    // HipBackend, residual checks, placement search
 #include "ks_vectors.hpp"    // n x r vectors in HBM: back-transformation, column residuals and Gram matrices without a download
 
+namespace {
+
+// the guards the four grid operators share; make(D{}, who) builds the operator of element type D
+template <class F> int grid_operator_entry(ks_ctx* ctx, int dtype, ks_operator** out, const std::string& who, F make) {
+  return guarded([&] {
+    KS_REQUIRE(ctx && out, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
+    KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, who + ": single-GPU contexts only (the grid is not partitioned across ranks)");
+    ctx->use();
+    *out = dtype == KS_F64 ? make(double{}, who) : make(cd{}, who);
+  });
+}
+
+// the element type of the four host grid matrices: fill(H{}, who) writes the matrix with entries of host type H
+template <class F> int grid_host_entry(int dtype, const std::string& who, F fill) {
+  return guarded([&] {
+    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
+    if (dtype == KS_F64) fill(double{}, who);
+    else fill(cplx{}, who);
+  });
+}
+
+}  // namespace
+
 // ================================================================================================
 // C ABI
 // ================================================================================================
@@ -511,49 +535,29 @@ int ks_operator_product(ks_ctx* ctx, int nops, ks_operator* const* ops, ks_opera
 }
 
 int ks_operator_grid(ks_ctx* ctx, int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential, ks_operator** out) {
-  return guarded([&] {
-    KS_REQUIRE(ctx && out, KS_ERR_ARGUMENT, "null argument");
-    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
-    KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, "ks_operator_grid: single-GPU contexts only (the grid is not partitioned across ranks)");
-    ctx->use();
-    *out = dtype == KS_F64 ? make_grid<double>(ctx, "ks_operator_grid", ndim, dims, taps, potential, nullptr, nullptr)
-                           : make_grid<cd>(ctx, "ks_operator_grid", ndim, dims, taps, potential, nullptr, nullptr);
+  return grid_operator_entry(ctx, dtype, out, "ks_operator_grid", [&](auto d, const std::string& who) {
+    return make_grid<decltype(d)>(ctx, who, ndim, dims, taps, potential, nullptr, nullptr);
   });
 }
 
 int ks_operator_grid_star(ks_ctx* ctx, int ndim, const int64_t* dims, int radius, int dtype, const void* taps, const void* potential,
                           ks_operator** out) {
-  return guarded([&] {
-    KS_REQUIRE(ctx && out, KS_ERR_ARGUMENT, "null argument");
-    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
-    KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, "ks_operator_grid_star: single-GPU contexts only (the grid is not partitioned across ranks)");
-    ctx->use();
-    *out = dtype == KS_F64 ? make_grid<double>(ctx, "ks_operator_grid_star", ndim, dims, taps, potential, nullptr, nullptr, radius)
-                           : make_grid<cd>(ctx, "ks_operator_grid_star", ndim, dims, taps, potential, nullptr, nullptr, radius);
+  return grid_operator_entry(ctx, dtype, out, "ks_operator_grid_star", [&](auto d, const std::string& who) {
+    return make_grid<decltype(d)>(ctx, who, ndim, dims, taps, potential, nullptr, nullptr, radius);
   });
 }
 
 int ks_operator_grid_periodic(ks_ctx* ctx, int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential,
                               const int* periodic, const void* wrap, ks_operator** out) {
-  return guarded([&] {
-    KS_REQUIRE(ctx && out, KS_ERR_ARGUMENT, "null argument");
-    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
-    KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, "ks_operator_grid_periodic: single-GPU contexts only (the grid is not partitioned across ranks)");
-    ctx->use();
-    *out = dtype == KS_F64 ? make_grid<double>(ctx, "ks_operator_grid_periodic", ndim, dims, taps, potential, periodic, wrap)
-                           : make_grid<cd>(ctx, "ks_operator_grid_periodic", ndim, dims, taps, potential, periodic, wrap);
+  return grid_operator_entry(ctx, dtype, out, "ks_operator_grid_periodic", [&](auto d, const std::string& who) {
+    return make_grid<decltype(d)>(ctx, who, ndim, dims, taps, potential, periodic, wrap);
   });
 }
 
 int ks_operator_grid_var(ks_ctx* ctx, int ndim, const int64_t* dims, int dtype, const void* taps, const double* coeff, const void* potential,
                          ks_operator** out) {
-  return guarded([&] {
-    KS_REQUIRE(ctx && out, KS_ERR_ARGUMENT, "null argument");
-    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
-    KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, "ks_operator_grid_var: single-GPU contexts only (the grid is not partitioned across ranks)");
-    ctx->use();
-    *out = dtype == KS_F64 ? make_grid_var<double>(ctx, "ks_operator_grid_var", ndim, dims, taps, coeff, potential)
-                           : make_grid_var<cd>(ctx, "ks_operator_grid_var", ndim, dims, taps, coeff, potential);
+  return grid_operator_entry(ctx, dtype, out, "ks_operator_grid_var", [&](auto d, const std::string& who) {
+    return make_grid_var<decltype(d)>(ctx, who, ndim, dims, taps, coeff, potential);
   });
 }
 
@@ -1706,37 +1710,29 @@ int ks_host_csr_plan(int64_t nrows_local, int64_t ncols, int64_t nnz, const void
 
 int ks_host_grid_matrix(int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential, int64_t* rowptr, int32_t* colidx,
                         void* val, int64_t cap, int64_t* nnz) {
-  return guarded([&] {
-    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
-    if (dtype == KS_F64) grid::host_matrix_entry<double>("ks_host_grid_matrix", ndim, dims, taps, potential, nullptr, nullptr, rowptr, colidx, val, cap, nnz);
-    else grid::host_matrix_entry<cplx>("ks_host_grid_matrix", ndim, dims, taps, potential, nullptr, nullptr, rowptr, colidx, val, cap, nnz);
+  return grid_host_entry(dtype, "ks_host_grid_matrix", [&](auto h, const std::string& who) {
+    grid::host_matrix_entry<decltype(h)>(who, ndim, dims, taps, potential, nullptr, nullptr, rowptr, colidx, val, cap, nnz);
   });
 }
 
 int ks_host_grid_matrix_star(int ndim, const int64_t* dims, int radius, int dtype, const void* taps, const void* potential, int64_t* rowptr,
                              int32_t* colidx, void* val, int64_t cap, int64_t* nnz) {
-  return guarded([&] {
-    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
-    if (dtype == KS_F64) grid::host_matrix_star_entry<double>("ks_host_grid_matrix_star", ndim, dims, radius, taps, potential, rowptr, colidx, val, cap, nnz);
-    else grid::host_matrix_star_entry<cplx>("ks_host_grid_matrix_star", ndim, dims, radius, taps, potential, rowptr, colidx, val, cap, nnz);
+  return grid_host_entry(dtype, "ks_host_grid_matrix_star", [&](auto h, const std::string& who) {
+    grid::host_matrix_star_entry<decltype(h)>(who, ndim, dims, radius, taps, potential, rowptr, colidx, val, cap, nnz);
   });
 }
 
 int ks_host_grid_matrix_periodic(int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential, const int* periodic,
                                  const void* wrap, int64_t* rowptr, int32_t* colidx, void* val, int64_t cap, int64_t* nnz) {
-  return guarded([&] {
-    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
-    if (dtype == KS_F64) grid::host_matrix_entry<double>("ks_host_grid_matrix_periodic", ndim, dims, taps, potential, periodic, wrap, rowptr, colidx, val, cap, nnz);
-    else grid::host_matrix_entry<cplx>("ks_host_grid_matrix_periodic", ndim, dims, taps, potential, periodic, wrap, rowptr, colidx, val, cap, nnz);
+  return grid_host_entry(dtype, "ks_host_grid_matrix_periodic", [&](auto h, const std::string& who) {
+    grid::host_matrix_entry<decltype(h)>(who, ndim, dims, taps, potential, periodic, wrap, rowptr, colidx, val, cap, nnz);
   });
 }
 
 int ks_host_grid_var_matrix(int ndim, const int64_t* dims, int dtype, const void* taps, const double* coeff, const void* potential,
                             int64_t* rowptr, int32_t* colidx, void* val, int64_t cap, int64_t* nnz) {
-  return guarded([&] {
-    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
-    if (dtype == KS_F64) grid::host_var_matrix_entry<double>("ks_host_grid_var_matrix", ndim, dims, taps, coeff, potential, rowptr, colidx, val, cap, nnz);
-    else grid::host_var_matrix_entry<cplx>("ks_host_grid_var_matrix", ndim, dims, taps, coeff, potential, rowptr, colidx, val, cap, nnz);
+  return grid_host_entry(dtype, "ks_host_grid_var_matrix", [&](auto h, const std::string& who) {
+    grid::host_var_matrix_entry<decltype(h)>(who, ndim, dims, taps, coeff, potential, rowptr, colidx, val, cap, nnz);
   });
 }
 

@@ -2,6 +2,7 @@
 """The matrix-free grid operator (ks_operator_grid) against the stored layouts, in the solver's own access pattern:
 
     python tools/grid_bench.py [--sizes 216,100] [--rounds 7] [--chains 5] [--cycles 20] [--no-solve] [--periodic] [--radius R] [--variable]
+                               [--complex [--wide]]
 
 Float64, 7-point -Laplacian (+ a harmonic potential) on m x m x m grids.  Per size, in ONE process:
 
@@ -26,6 +27,10 @@ Float64, 7-point -Laplacian (+ a harmonic potential) on m x m x m grids.  Per si
                (c) grid_variable_operator without a diagonal       24 n bytes
                (d) grid_operator with a potential                  24 n bytes: (a) of the plain run, the constant-coefficient floor
              and the solve on (a) and (b).
+             --complex runs the grid operators of the run that the other switches select -- (a) and (c); --periodic: (e) alone;
+             --variable: (a), (c), (d) -- in the same rounds with ComplexF64 taps, potential and vectors (twice the bytes; c stays
+             Float64): products only, no stored matrix and no solve.  --wide puts them on the m^2 x 1 x m grid, which takes the
+             one-row tiles.
              The HIP-event time is taken per round as well (`event_rounds`): its mean and max - min are what two builds are
              compared by.
   solve      iterations/s of nev = 20, mindim / maxdim = 20 / 40, :SR on (a) and (b): `cycles` timed restart cycles after 3 warm-up
@@ -56,8 +61,8 @@ def stats(v):
                 rounds=[round(float(x), 3) for x in v])
 
 
-def bench_products(ctx, ops, n, rounds, chains):
-    ws = ks.ArnoldiWorkspace(n, MAXDIM, np.float64, ctx=ctx)
+def bench_products(ctx, ops, n, rounds, chains, dtype=np.float64):
+    ws = ks.ArnoldiWorkspace(n, MAXDIM, dtype, ctx=ctx)
     ws.fill_uniform(0, 1)
     us = {name: [] for name in ops}
     for name, op in ops.items():      # warm-up: every operator over every column
@@ -129,7 +134,14 @@ def main():
     ap.add_argument("--periodic", action="store_true", help="add (e) the periodic grid operator and (f) its stored matrix")
     ap.add_argument("--radius", type=int, default=None, help="2, 3 or 4: (a), (b), (c) with the star stencil of order 2 R")
     ap.add_argument("--variable", action="store_true", help="the variable-coefficient operator against its stored matrix and the constant-coefficient floor")
+    ap.add_argument("--complex", action="store_true", help="the selected grid operators alone, in ComplexF64: products only")
+    ap.add_argument("--wide", action="store_true", help="with --complex: the m^2 x 1 x m grid (one-row tiles)")
     args = ap.parse_args()
+    if args.complex:
+        main_complex(args)
+        return
+    if args.wide:
+        raise SystemExit("--wide belongs to --complex")
     if args.variable:
         main_variable(args)
         return
@@ -307,6 +319,53 @@ def main_variable(args):
             out["blocks"] = {name: s.ws.sstep_info["blocks"] for name, s in runs.items()}
             for s in runs.values():
                 s.ws.close()
+        report(out, prod, m, n, args)
+        for op in ops.values():
+            op.close()
+
+
+def main_complex(args):
+    """--complex: the grid operators of the selected run alone, every tap and the potential times 1 + 0.25i."""
+    from arnoldimethod_jl_amd import extras
+
+    R = 1 if args.radius is None else args.radius
+    if R not in (1, 2, 3, 4) or (R > 1 and (args.periodic or args.variable)) or (args.periodic and args.variable):
+        raise SystemExit("--complex takes one of --periodic, --radius 2 / 3 / 4 and --variable")
+    phase = 1.0 + 0.25j
+    ctx = ks.Context(0)
+    for m in (int(s) for s in args.sizes.split(",")):
+        shape, n = ((m * m, 1, m) if args.wide else (m, m, m)), m ** 3
+        V = phase * ks.matrices.harmonic_potential(shape)
+        t0 = time.perf_counter()
+        if args.variable:
+            c = jump_coefficient(shape)
+            taps, diag = extras.diffusion_terms(shape, c, potential=V.real)
+            ops = {
+                "a_var_diagonal": ks.grid_variable_operator(shape, phase * taps, c, phase * diag, ctx=ctx),
+                "c_var_plain": ks.grid_variable_operator(shape, phase * LAPLACE, c, ctx=ctx),
+                "d_grid_potential": ks.grid_operator(shape, phase * LAPLACE, V, ctx=ctx),
+            }
+            by = {"a_var_diagonal": 56.0 * n, "c_var_plain": 40.0 * n, "d_grid_potential": 48.0 * n}
+        elif args.periodic:
+            ops = {"e_grid_periodic": ks.grid_operator(shape, phase * LAPLACE, V, ctx=ctx, periodic=tuple(e >= 3 for e in shape))}
+            by = {"e_grid_periodic": 48.0 * n}
+        else:
+            taps = phase * (LAPLACE if R == 1 else extras.fd_laplacian_taps(3, 2 * R))
+            ops = {
+                "a_grid_potential": ks.grid_operator(shape, taps, V, ctx=ctx, radius=R),
+                "c_grid_plain": ks.grid_operator(shape, taps, ctx=ctx, radius=R),
+            }
+            by = {"a_grid_potential": 48.0 * n, "c_grid_plain": 32.0 * n}
+        setup_s = time.perf_counter() - t0
+        out = dict(m=m, n=n, shape=list(shape), dtype="complex128", radius=R, variable=args.variable, periodic=args.periodic,
+                   setup_seconds=round(setup_s, 2), chains=args.chains, products_per_round=args.chains * MAXDIM)
+        prod = bench_products(ctx, ops, n, args.rounds, args.chains, np.complex128)
+        for name, s in prod.items():
+            s["bytes_per_product"] = by[name]
+            s["hbm_fraction_at_mean"] = by[name] / (s["mean"] * 1e-6) / PEAK
+            s["hbm_fraction_of_kernels"] = by[name] / (s["event_us"] * 1e-6) / PEAK
+        out["us_per_product"] = prod
+        args.no_solve = True
         report(out, prod, m, n, args)
         for op in ops.values():
             op.close()
