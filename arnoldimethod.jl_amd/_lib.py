@@ -166,6 +166,7 @@ PROTOTYPES = {
     "ks_host_sortschur": [i32, vp, i32, i32, i32, vp, i32, i32, i32, i32],
     "ks_host_givens": [i32, vp, vp, P(dbl), vp, vp],
     "ks_host_csr_plan": [i64, i64, i64, vp, vp, vp, i32, i32, i32, i32, i32, i64, i64, P(C.c_int), P(C.c_int), P(dbl), P(dbl), vp, vp, vp, vp, i64, vp, i32],
+    "ks_host_halo_plan": [i64, i64, i64, vp, vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i64, vp],
     "ks_host_grid_matrix": [i32, vp, i32, vp, vp, vp, vp, vp, i64, P(i64)],
     "ks_host_grid_matrix_periodic": [i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, P(i64)],
     "ks_host_grid_matrix_star": [i32, vp, i32, i32, vp, vp, vp, vp, vp, i64, P(i64)],

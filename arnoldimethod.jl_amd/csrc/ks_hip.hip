@@ -37,6 +37,8 @@ using ksd::kBlock;
 
 #include "ks_context.hpp"    // errors, ks_ctx, transports
 #include "ks_csr_layout.hpp" // host-only: which layout a stored matrix gets, and its host arrays
+#include "ks_halo_plan.hpp"  // host-only: what a distributed row block exchanges with its neighbours, and the peer-to-peer table
+#include "ks_halo.hpp"       // ... uploaded: ghost vector, transport buffers, the exchange in front of a product
 #include "ks_operators.hpp"  // ks_operator and its layouts
 #include "ks_sptrsv.hpp"     // shift-invert operator from triangular factors (sparse triangular solves)
 #include "ks_tridiag.hpp"    // tridiagonal shift-invert operator: factored once on the host (ks_tridiag_plan.hpp), applied in HBM
@@ -252,140 +254,18 @@ int ks_operator_csr_dist(ks_ctx* ctx, int64_t nrows_local, int64_t nghost, int64
   return guarded([&] {
     KS_REQUIRE(ctx && out && rowptr, KS_ERR_ARGUMENT, "null argument");
     ctx->use();
-    KS_REQUIRE(nrows_local < (int64_t)2147483647 && nghost < (int64_t)2147483647 - nrows_local, KS_ERR_ARGUMENT,
-               "local-extended column range must fit int32");
-    std::vector<int64_t> rp(nrows_local + 1);
-    KS_REQUIRE(rowptr[0] == 0 && rowptr[nrows_local] == nnz, KS_ERR_ARGUMENT, "row pointer does not match nnz");
-    for (int64_t i = 0; i <= nrows_local; ++i) {
-      KS_REQUIRE(i == 0 || (rowptr[i] >= rowptr[i - 1] && rowptr[i] <= nnz), KS_ERR_ARGUMENT,
-                 "pointer array is not monotone within [0, nnz]");
-      rp[i] = rowptr[i];
-    }
-    std::vector<int32_t> ci(colidx, colidx + nnz);
-    for (int64_t p = 0; p < nnz; ++p)
-      KS_REQUIRE(ci[p] >= 0 && ci[p] < nrows_local + nghost, KS_ERR_ARGUMENT, "local-extended column index out of range");
+    std::vector<int64_t> rp;
+    std::vector<int32_t> ci;
+    build_csr_dist_host(nrows_local, nghost, nnz, rowptr, colidx, rp, ci);
     dispatch_dtype(dtype, [&](auto tag) {
-      using T = decltype(tag);
-      using D = typename DevT<T>::type;
+      using D = typename DevT<decltype(tag)>::type;
+      // planned on the host (ks_halo_plan.hpp: every check of the caller's lists), then uploaded
+      const HaloPlan plan = plan_halo(rp, ci, nrows_local, nghost, ctx->rank, nneigh, neigh, send_ptr, send_idx, recv_cnt);
       std::vector<D> vv(static_cast<const D*>(val), static_cast<const D*>(val) + nnz);
-      // ghost slots owned by lower ranks (they precede the local columns in the global order: column blocks keep the
-      // single-GPU summation order); -1: the neighbour list is not ascending by rank with consecutive slots -> no column blocks
-      int64_t nlow = 0;
-      {
-        bool above = false, ok = true;
-        for (int p = 0; p < nneigh; ++p) {
-          KS_REQUIRE(recv_cnt[p] >= 0, KS_ERR_ARGUMENT, "negative receive count");
-          if (neigh[p] < ctx->rank) { if (above) ok = false; nlow += recv_cnt[p]; }
-          else above = true;
-        }
-        if (!ok) nlow = -1;
-      }
-      CsrOp<D>* op = make_csr<D>(ctx, nrows_local, nnz, rp, ci, vv, nlow >= 0 ? CbMode::DistributedRowBlock : CbMode::None, nghost, std::max<int64_t>(nlow, 0));
-      std::unique_ptr<CsrOp<D>> guard(op);
-      op->nghost = nghost;
-      op->p2p_halo = ctx->p2p.attached;
-      {
-        // rows that reference ghost columns: all of them lie outside ONE interval [ghost_lo_end, ghost_hi_begin) -- the
-        // largest gap between such rows (a slab of a structured grid: everything between its first and its last plane).
-        // Workgroups whose rows fall inside never wait for the exchange (fused halo, ks_p2p.hpp).
-        int64_t best_a = 0, best_b = nrows_local, prev = -1;
-        bool any = false;
-        int64_t gap_best = -1;
-        for (int64_t r = 0; r < nrows_local; ++r) {
-          bool touches = false;
-          for (int64_t q = rp[r]; q < rp[r + 1] && !touches; ++q) touches = ci[q] >= nrows_local;
-          if (!touches) continue;
-          any = true;
-          if (r - prev - 1 > gap_best) { gap_best = r - prev - 1; best_a = prev + 1; best_b = r; }
-          prev = r;
-        }
-        if (any && nrows_local - prev - 1 > gap_best) { best_a = prev + 1; best_b = nrows_local; }
-        op->ghost_lo_end = any ? best_a : 0;
-        op->ghost_hi_begin = any ? best_b : nrows_local;
-      }
-      if (!op->p2p_halo) {
-        KS_HIP(hipMalloc(&op->ghost, std::max<size_t>((size_t)nghost * sizeof(D), 16)));
-        KS_HIP(hipMemset(op->ghost, 0, std::max<size_t>((size_t)nghost * sizeof(D), 16)));
-      }
-      op->neigh.assign(neigh, neigh + nneigh);
-      op->send_ptr.assign(send_ptr, send_ptr + nneigh + 1);
-      op->recv_ptr.assign(nneigh + 1, 0);
-      for (int p = 0; p < nneigh; ++p) op->recv_ptr[p + 1] = op->recv_ptr[p] + recv_cnt[p];
-      KS_REQUIRE(op->recv_ptr[nneigh] == nghost, KS_ERR_ARGUMENT, "recv counts do not add up to nghost");
-      // split the send lists into contiguous runs (sent in place) and scattered ones (packed)
-      std::vector<int32_t> packed;
-      op->send_first.assign(nneigh, -1);
-      op->pack_ptr.assign(nneigh + 1, 0);
-      for (int p = 0; p < nneigh; ++p) {
-        const int64_t a = send_ptr[p], b = send_ptr[p + 1];
-        bool contiguous = b > a;
-        for (int64_t q = a; q < b; ++q) {
-          KS_REQUIRE(send_idx[q] >= 0 && send_idx[q] < nrows_local, KS_ERR_ARGUMENT, "send index out of range");
-          if (q > a && send_idx[q] != send_idx[q - 1] + 1) contiguous = false;
-        }
-        if (contiguous) op->send_first[p] = send_idx[a];
-        else packed.insert(packed.end(), send_idx + a, send_idx + b);
-        op->pack_ptr[p + 1] = (int64_t)packed.size();
-      }
-      op->nscatter = (int64_t)packed.size();
-      KS_HIP(hipMalloc(&op->sendbuf, std::max<size_t>(packed.size() * sizeof(D), 16)));
-      KS_HIP(hipMalloc(&op->send_idx, std::max<size_t>(packed.size() * 4, 16)));
-      if (!packed.empty()) KS_HIP(hipMemcpy(op->send_idx, packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
-      KS_REQUIRE(nneigh == 0 || ctx->distributed(), KS_ERR_ARGUMENT, "halo plan needs a distributed context");
-      if (ctx->hc.exchange) {
-        KS_HIP(hipHostMalloc(&op->hsend, std::max<size_t>((size_t)send_ptr[nneigh] * sizeof(D), 16)));
-        KS_HIP(hipHostMalloc(&op->hrecv, std::max<size_t>((size_t)nghost * sizeof(D), 16)));
-      }
-      if (op->p2p_halo) {
-        // COLLECTIVE in peer-to-peer mode: every rank publishes where its ghost vector lives in its shared
-        // arena and, per sender, at which offset that sender's entries go (and how many it expects)
-        auto& P = ctx->p2p;
-        const int R = ctx->nranks;
-        KS_REQUIRE(nneigh <= ksd::kP2pMaxNeigh, KS_ERR_ARGUMENT, "peer-to-peer halo supports at most 16 neighbours per rank");
-        op->ghost_stride = round_up(std::max<int64_t>(nghost, 1), 32);
-        const size_t bytes = (size_t)round_up(2 * op->ghost_stride * (int64_t)sizeof(D), 256);
-        KS_REQUIRE(P.arena_used + bytes <= P.arena_bytes, KS_ERR_ARGUMENT,
-                   "ghost vectors do not fit the shared arena (raise KS_P2P_ARENA_MB)");
-        op->arena_lo = P.arena_used;
-        op->arena_hi = P.arena_used + bytes;
-        P.arena_used = op->arena_hi;
-        op->ghost = reinterpret_cast<D*>(static_cast<char*>(P.region) + P.arena_off + op->arena_lo);
-        KS_HIP(hipMemset(op->ghost, 0, bytes));
-        KS_HIP(hipDeviceSynchronize());
-        std::vector<int64_t> row((size_t)2 + 2 * R, 0);
-        row[0] = (int64_t)(P.arena_off + op->arena_lo);
-        row[1] = op->ghost_stride;
-        for (int p = 0; p < nneigh; ++p) {
-          KS_REQUIRE(neigh[p] >= 0 && neigh[p] < R, KS_ERR_ARGUMENT, "bad neighbour rank");
-          row[2 + 2 * neigh[p]] = op->recv_ptr[p];
-          row[3 + 2 * neigh[p]] = recv_cnt[p];
-        }
-        const std::vector<int64_t> tab = p2p_allgather_i64(ctx, row);
-        const size_t K = row.size();
-        ksd::HaloArgs a{};
-        a.nneigh = nneigh;
-        a.nrecv = 0;
-        std::vector<int32_t> all;
-        for (int p = 0; p < nneigh; ++p) {
-          const int q = neigh[p];
-          const int64_t sc = send_ptr[p + 1] - send_ptr[p];
-          a.send_ptr[p] = send_ptr[p];
-          a.send_ptr[p + 1] = send_ptr[p + 1];
-          const int64_t* tq = tab.data() + (size_t)q * K;
-          KS_REQUIRE(tq[3 + 2 * ctx->rank] == sc, KS_ERR_ARGUMENT,
-                     "halo plans disagree: rank " + std::to_string(q) + " expects " + std::to_string(tq[3 + 2 * ctx->rank]) +
-                         " entries from rank " + std::to_string(ctx->rank) + ", which sends " + std::to_string(sc));
-          a.dst[p] = static_cast<char*>(P.peer[q]) + tq[0] + tq[2 + 2 * ctx->rank] * (int64_t)sizeof(D);
-          a.dst_stride[p] = tq[1];
-          a.flag_dst[p] = static_cast<uint64_t*>(P.peer[q]) + ksd::p2p_ll_words(R, P.cap) + ctx->rank;
-          if (recv_cnt[p] > 0) a.recv_from[a.nrecv++] = q;
-          all.insert(all.end(), send_idx + send_ptr[p], send_idx + send_ptr[p + 1]);
-        }
-        op->hargs = a;
-        KS_HIP(hipMalloc(&op->send_idx_all, std::max<size_t>(all.size() * 4, 16)));
-        if (!all.empty()) KS_HIP(hipMemcpy(op->send_idx_all, all.data(), all.size() * 4, hipMemcpyHostToDevice));
-      }
-      *out = guard.release();
+      std::unique_ptr<CsrOp<D>> op(make_csr<D>(ctx, nrows_local, nnz, rp, ci, vv, plan.nlow >= 0 ? CbMode::DistributedRowBlock : CbMode::None, nghost,
+                                               std::max<int64_t>(plan.nlow, 0)));
+      op->halo.upload(ctx, plan);  // COLLECTIVE in peer-to-peer mode
+      *out = op.release();
     });
   });
 }
@@ -1705,6 +1585,33 @@ int ks_host_csr_plan(int64_t nrows_local, int64_t ncols, int64_t nnz, const void
       }
       for (int b = 0; cb_bounds && b < (int)P.cb_bounds.size() && b < cb_cap; ++b) cb_bounds[b] = P.cb_bounds[b];
     });
+  });
+}
+
+int ks_host_halo_plan(int64_t nrows_local, int64_t nghost, int64_t nnz, const int64_t* rowptr, const int32_t* colidx, int nneigh,
+                      const int32_t* neigh, const int64_t* send_ptr, const int32_t* send_idx, const int64_t* recv_cnt, int rank, int elem_size,
+                      int64_t* facts, int64_t* recv_ptr, int64_t* send_first, int64_t* pack_ptr, int32_t* packed, int64_t packed_cap,
+                      int64_t* p2p_ghost) {
+  return guarded([&] {
+    KS_REQUIRE(rowptr, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(elem_size == 8 || elem_size == 16, KS_ERR_ARGUMENT, "element size must be 8 or 16");
+    std::vector<int64_t> rp;
+    std::vector<int32_t> ci;
+    build_csr_dist_host(nrows_local, nghost, nnz, rowptr, colidx, rp, ci);
+    const HaloPlan P = plan_halo(rp, ci, nrows_local, nghost, rank, nneigh, neigh, send_ptr, send_idx, recv_cnt);
+    if (facts) {
+      const int64_t f[KS_HALO_NFACTS] = {P.nlow, P.ghost_lo_end, P.ghost_hi_begin, P.nscatter};
+      std::copy(f, f + KS_HALO_NFACTS, facts);
+    }
+    if (recv_ptr) std::copy(P.recv_ptr.begin(), P.recv_ptr.end(), recv_ptr);
+    if (send_first) std::copy(P.send_first.begin(), P.send_first.end(), send_first);
+    if (pack_ptr) std::copy(P.pack_ptr.begin(), P.pack_ptr.end(), pack_ptr);
+    if (packed) std::copy(P.packed.begin(), P.packed.begin() + std::min<int64_t>(P.nscatter, std::max<int64_t>(packed_cap, 0)), packed);
+    if (p2p_ghost) {
+      const P2pGhost g = p2p_ghost_size(P, (size_t)elem_size);
+      p2p_ghost[0] = g.stride;
+      p2p_ghost[1] = (int64_t)g.bytes;
+    }
   });
 }
 

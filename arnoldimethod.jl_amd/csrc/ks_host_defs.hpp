@@ -1,5 +1,5 @@
-// What the host-only code (ks_csr_layout.hpp) shares with the device side: the launch-shape constants the CSR layouts are planned
-// around, the error type and the two small helpers.  No HIP header: a plain host compiler can build this.
+// What the host-only code (ks_csr_layout.hpp, ks_halo_plan.hpp) shares with the device side: the launch-shape constants the CSR
+// layouts are planned around, the neighbour limit of the peer-to-peer halo, the error type and the two small helpers.  No HIP header: a plain host compiler can build this.
 #pragma once
 
 #include <cstdint>
@@ -14,6 +14,7 @@ constexpr int kSpmvRows = 256;        // k_spmv_csr: rows per block at most
 constexpr int kSpmvCapBytes = 32768;  // k_spmv_csr: LDS for the products of a block: NI * 256 * sizeof(T) <= 32 KiB
 constexpr int kCbMaxBlocks = 8;       // k_spmv_csr_cb: column blocks of one launch (CbArgs)
 constexpr int kStencilSlots = 32;     // k_spmv_stencil: dictionary slots (StencilDict)
+constexpr int kP2pMaxNeigh = 16;      // peer-to-peer halo: neighbours of a rank (HaloArgs, ks_p2p.hpp)
 }  // namespace ksd
 
 namespace {

@@ -1,7 +1,7 @@
 // operators: anything with mul!(y, A, x) (src/run.jl:21-22) -- stored sparse matrices in their device layouts, dense matrices, host / device callbacks
 // Part of the ONE translation unit of libkschur_hip.so: included by ks_hip.hip, in this order --
 //     ks_context.hpp -> ks_operators.hpp -> ks_workspace.hpp -> ks_backend.hpp -> (C ABI in ks_hip.hip)
-// -- and not meant to be included on its own (needs ks_context.hpp and ks_csr_layout.hpp).
+// -- and not meant to be included on its own (needs ks_context.hpp, ks_csr_layout.hpp and ks_halo.hpp).
 #pragma once
 // ------------------------------------------------------------------------------------------------
 // operators
@@ -63,6 +63,8 @@ template <class D> struct CsrOp : ks_operator {
   void* smask = nullptr;
   void* smask2 = nullptr;    // == smask (the array is padded to an even number of rows): masks of rows 2t, 2t+1 in one word
   ksd::StencilDict<D> sdict{};
+  int nstencil_local = 0;            // leading slots of the stencil dictionary; the rest name ghost columns only
+  mutable bool split_said = false;   // (KS_DIST_SPLIT_DEBUG: one line per operator)
   // sliced-ELLPACK layout (k_spmv_sell): slices of 64 rows, column-major, padded to the slice's longest row
   void* sliceptr = nullptr;  // entry offsets of the slices, same integer type as rowptr
   int32_t* sperm = nullptr;  // slice position -> row (sigma > 1 only)
@@ -76,39 +78,11 @@ template <class D> struct CsrOp : ks_operator {
   int32_t* ddelta = nullptr;
   int dvi_unroll = 8;
   int dvi_rpt = 1;          // rows per thread of k_spmv_dvi
-  // halo plan (distributed)
-  int64_t nghost = 0;
-  D* ghost = nullptr;
-  D* sendbuf = nullptr;
-  int32_t* send_idx = nullptr;
-  std::vector<int> neigh;
-  std::vector<int64_t> send_ptr, recv_ptr;
-  std::vector<int64_t> send_first;  // >= 0: neighbour p's rows are the contiguous run starting here (no packing)
-  std::vector<int64_t> pack_ptr;    // offset of neighbour p's packed values in sendbuf (scattered lists only)
-  int64_t nscatter = 0;             // number of packed entries (send_idx holds only these)
-  // peer-to-peer halo (ks_p2p.hpp): ghost lives (double-buffered) in this rank's shared arena, neighbours
-  // store into it directly
-  // host-staged halo (ks_ctx_create_hostcomm): pinned send / receive images of the plan
-  D* hsend = nullptr;
-  D* hrecv = nullptr;
-  bool p2p_halo = false;
-  int64_t ghost_stride = 0;         // elements between the two ghost slots
-  int nstencil_local = 0;            // leading slots of the stencil dictionary; the rest name ghost columns only
-  mutable bool split_said = false;   // (KS_DIST_SPLIT_DEBUG: one line per operator)
-  int64_t ghost_lo_end = 0, ghost_hi_begin = 0;  // only rows < ghost_lo_end or >= ghost_hi_begin reference ghost columns (fused exchange)
-  size_t arena_lo = 0, arena_hi = 0;
-  int32_t* send_idx_all = nullptr;  // every send entry (contiguous runs included), neighbour by neighbour
-  ksd::HaloArgs hargs{};
+  // ghost vector and exchange of a distributed row block (ks_halo.hpp; one GPU: empty)
+  Halo<D> halo;
 
   ~CsrOp() override {
     (void)hipFree(rowptr); (void)hipFree(colidx); (void)hipFree(val); (void)hipFree(blkptr); (void)hipFree(blkrow); (void)hipFree(smask); (void)hipFree(sliceptr); (void)hipFree(sperm); (void)hipFree(blkpart); (void)hipFree(lpart); (void)hipFree(lrow); (void)hipFree(lfirst);
-    if (p2p_halo) {
-      if (ctx->p2p.arena_used == arena_hi) ctx->p2p.arena_used = arena_lo;  // stack discipline; otherwise kept until the context dies
-    } else {
-      (void)hipFree(ghost);
-    }
-    (void)hipHostFree(hsend); (void)hipHostFree(hrecv);
-    (void)hipFree(sendbuf); (void)hipFree(send_idx); (void)hipFree(send_idx_all);
     (void)hipFree(codes); (void)hipFree(ddelta);
   }
   // the CSR-row-block kernel of THIS operator's arrays on x -> y, continuing the row sums in `yacc` (column-blocked
@@ -263,74 +237,10 @@ template <class D> struct CsrOp : ks_operator {
     const D* x = static_cast<const D*>(xv);
     D* y = static_cast<D*>(yv);
     hipStream_t s = ctx->stream;
-    // peer-to-peer mode: sequence number and ghost slot of this exchange (host counter, ks_p2p.hpp); the stencil and the
-    // CSR-row-block kernels do the exchange themselves, every other layout gets the push kernel in front
-    ksd::HaloFused hf{};
-    const D* xg = ghost;
-    if (p2p_halo && !neigh.empty()) {
-      uint32_t seq = ctx->p2p.hseq + 1u;
-      if (seq == 0u) seq = 1u;
-      ctx->p2p.hseq = seq;
-      xg = ghost + (int64_t)(seq & 1u) * ghost_stride;
-      static const int fuse_env = env_int("KS_HALO_FUSED", 1);
-      const bool fusable = fuse_env && n_local > 0 && cblocks.empty() && ndvi == 0 && nslices == 0;
-      const int64_t total = send_ptr.back();
-      if (fusable) {
-        hf.enabled = 1;
-        hf.seq = seq;
-        // pushers: ~8 entries per thread (two trips of four independent entries), at most 64 workgroups -- each pusher ends
-        // with a system-scope release fence (an L2 write-back), which is what an SpMV launch can afford only a few of
-        static const int npush_env = env_int("KS_HALO_NPUSH", 0);
-        hf.npush = npush_env > 0 ? npush_env : (int)std::max<int64_t>(1, std::min<int64_t>((total + 2047) / 2048, 64));
-        hf.send_idx = send_idx_all;
-        hf.counter = ctx->p2p.hstate + 1;
-        hf.ghost_lo_end = ghost_lo_end;
-        hf.ghost_hi_begin = ghost_hi_begin;
-      } else {
-        const int gb = (int)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 512));
-        ksd::k_halo_push<D><<<gb, 256, 0, s>>>(x, send_idx_all, hargs, ctx->p2p.dev, ctx->p2p.hstate, seq,
-                                                 st ? &st->breakdown : nullptr);
-      }
-    } else if (!p2p_halo && !neigh.empty()) {
-      // neighbours whose send list is one contiguous run of rows (grid planes of a slab partition) are sent
-      // straight out of x; only genuinely scattered lists go through the pack kernel
-      if (nscatter > 0) {
-        const int gb = (int)std::min<int64_t>((nscatter + kBlock - 1) / kBlock, 4096);
-        ksd::k_gather<D><<<gb, kBlock, 0, s>>>(x, send_idx, sendbuf, nscatter, st);
-      }
-      constexpr int dpe = sizeof(D) / 8;  // doubles per element
-      if (ctx->hc.exchange) {
-        // host-staged: the same plan (in-place runs, packed lists, consecutive ghost slots) through pinned memory
-        const size_t np_ = neigh.size();
-        std::vector<const void*> sp_(np_);
-        std::vector<void*> rp_(np_);
-        std::vector<int64_t> sb_(np_), rb_(np_);
-        for (size_t p = 0; p < np_; ++p) {
-          const int64_t sc = send_ptr[p + 1] - send_ptr[p], rc = recv_ptr[p + 1] - recv_ptr[p];
-          if (sc > 0) {
-            const D* src = send_first[p] >= 0 ? x + send_first[p] : sendbuf + pack_ptr[p];
-            KS_HIP(hipMemcpyAsync(hsend + send_ptr[p], src, (size_t)sc * sizeof(D), hipMemcpyDeviceToHost, s));
-          }
-          sp_[p] = hsend + send_ptr[p]; sb_[p] = sc * (int64_t)sizeof(D);
-          rp_[p] = hrecv + recv_ptr[p]; rb_[p] = rc * (int64_t)sizeof(D);
-        }
-        KS_HIP(hipStreamSynchronize(s));
-        const int rc = ctx->hc.exchange(ctx->hc.user, (int)np_, neigh.data(), sp_.data(), sb_.data(), rp_.data(), rb_.data());
-        KS_REQUIRE(rc == 0, KS_ERR_COMM, "host exchange callback returned " + std::to_string(rc));
-        if (nghost > 0) KS_HIP(hipMemcpyAsync(ghost, hrecv, (size_t)nghost * sizeof(D), hipMemcpyHostToDevice, s));
-      } else {
-      KS_NCCL(ncclGroupStart());
-      for (size_t p = 0; p < neigh.size(); ++p) {
-        const int64_t sc = send_ptr[p + 1] - send_ptr[p], rc = recv_ptr[p + 1] - recv_ptr[p];
-        if (sc > 0) {
-          const D* src = send_first[p] >= 0 ? x + send_first[p] : sendbuf + pack_ptr[p];
-          KS_NCCL(ncclSend(src, (size_t)sc * dpe, ncclDouble, neigh[p], ctx->comm, s));
-        }
-        if (rc > 0) KS_NCCL(ncclRecv(ghost + recv_ptr[p], (size_t)rc * dpe, ncclDouble, neigh[p], ctx->comm, s));
-      }
-      KS_NCCL(ncclGroupEnd());
-      }
-    }
+    // the stencil and the CSR-row-block kernels take the exchange of the peer-to-peer transport into their own launch (hf)
+    const typename Halo<D>::Begun begun = halo.begin(x, st, n_local > 0 && cblocks.empty() && ndvi == 0 && nslices == 0);
+    const ksd::HaloFused& hf = begun.hf;
+    const D* xg = begun.xg;
     if (n_local > 0 && !cblocks.empty()) {
       // column-blocked CSR: one launch per column block; block b > 0 reads the partial row sums block b-1 left in y
       ProfScope ps(ctx, KSP_SPMV, (double)nnz * bytes_per_nnz + aux_bytes + 2.0 * sizeof(D) * n_local);
@@ -379,7 +289,7 @@ template <class D> struct CsrOp : ks_operator {
         if (ptr64) f(int64_t{});
         else f(int32_t{});
       };
-      if (nstencil > 0 && nghost == 0 && smask2 && n_local >= 2 && env_int("KS_STENCIL_PAIRS", 1)) {
+      if (nstencil > 0 && halo.plan.nghost == 0 && smask2 && n_local >= 2 && env_int("KS_STENCIL_PAIRS", 1)) {
         // two rows per lane, 16-byte gathers (no ghost columns: single GPU)
         const int nt = (int)(((n_local + 1) / 2 + kBlock - 1) / kBlock);
         if constexpr (std::is_same<D, double>::value) {
@@ -397,7 +307,7 @@ template <class D> struct CsrOp : ks_operator {
         KS_HIP(hipGetLastError());
         return;
       }
-      if (nstencil > 0 && nghost > 0 && !p2p_halo && smask2 && (stencil_mask_bytes == 1 || stencil_mask_bytes == 4) && n_local >= 2 * kBlock) {
+      if (nstencil > 0 && halo.plan.nghost > 0 && !halo.p2p && smask2 && (stencil_mask_bytes == 1 || stencil_mask_bytes == 4) && n_local >= 2 * kBlock) {
         // SPLIT PRODUCT of a rank on the collective transports (round 6c).  The ghost-aware kernel below is the one-row-per-lane
         // form (8-byte gathers: 16.2 us at the 8-way share of 216^3, 1.26e6 rows) where the paired kernel of the single-GPU path
         // takes 7.7 us.  Only the rows outside [ghost_lo_end, ghost_hi_begin) -- a slab's first and last plane -- reference ghost
@@ -411,7 +321,7 @@ template <class D> struct CsrOp : ks_operator {
         if constexpr (std::is_same<D, double>::value) {
           static const int split_env = env_int("KS_DIST_SPLIT", 1);
           const int nt1 = (int)((n_local + kBlock - 1) / kBlock);
-          const int nlow = (int)((ghost_lo_end + kBlock - 1) / kBlock), first_high = (int)(ghost_hi_begin / kBlock);
+          const int nlow = (int)((halo.plan.ghost_lo_end + kBlock - 1) / kBlock), first_high = (int)(halo.plan.ghost_hi_begin / kBlock);
           const int nhigh = nt1 - first_high;
           if (split_env && env_int("KS_STENCIL_PAIRS", 1) && nlow <= first_high && 4 * (nlow + nhigh) <= nt1 && nlow + nhigh > 0) {
             const int nt2 = (int)(((n_local + 1) / 2 + kBlock - 1) / kBlock);
@@ -430,12 +340,12 @@ template <class D> struct CsrOp : ks_operator {
             if (stencil_mask_bytes == 1) {
               ksd::k_spmv_stencil2<D, uint16_t><<<nt2, kBlock, 0, s>>>(static_cast<const uint16_t*>(smask2), sdict, nsl, x, y, n_local, nt2, st, shf, shift_theta, shift_sigma);
               ksd::k_spmv_stencil<D, uint8_t, 1><<<nlow + nhigh, kBlock, 0, s>>>(static_cast<const uint8_t*>(smask), sdict, nstencil, x, xg, y, n_local,
-                                                                                std::max<int64_t>(nghost, 0), nlow + nhigh, st, h0, hargs, ctx->p2p.dev, shift_on ? 1 : 0,
+                                                                                std::max<int64_t>(halo.plan.nghost, 0), nlow + nhigh, st, h0, halo.hargs, ctx->p2p.dev, shift_on ? 1 : 0,
                                                                                 shift_theta, shift_sigma, nlow, first_high - nlow);
             } else {
               ksd::k_spmv_stencil2<D, uint64_t><<<nt2, kBlock, 0, s>>>(static_cast<const uint64_t*>(smask2), sdict, nsl, x, y, n_local, nt2, st, shf, shift_theta, shift_sigma);
               ksd::k_spmv_stencil<D, uint32_t, 1><<<nlow + nhigh, kBlock, 0, s>>>(static_cast<const uint32_t*>(smask), sdict, nstencil, x, xg, y, n_local,
-                                                                                 std::max<int64_t>(nghost, 0), nlow + nhigh, st, h0, hargs, ctx->p2p.dev, shift_on ? 1 : 0,
+                                                                                 std::max<int64_t>(halo.plan.nghost, 0), nlow + nhigh, st, h0, halo.hargs, ctx->p2p.dev, shift_on ? 1 : 0,
                                                                                  shift_theta, shift_sigma, nlow, first_high - nlow);
             }
             KS_HIP(hipGetLastError());
@@ -451,9 +361,9 @@ template <class D> struct CsrOp : ks_operator {
           const int nt = (int)((n_local + kBlock * RPT - 1) / (kBlock * RPT));
           ksd::HaloFused h = hf;
           h.npush = std::min(h.npush, nt);
-          h.tile_shift = (h.enabled && ghost_lo_end < n_local) ? (int)((ghost_lo_end + kBlock * RPT - 1) / (kBlock * RPT)) % std::max(nt, 1) : 0;
+          h.tile_shift = (h.enabled && halo.plan.ghost_lo_end < n_local) ? (int)((halo.plan.ghost_lo_end + kBlock * RPT - 1) / (kBlock * RPT)) % std::max(nt, 1) : 0;
           ksd::k_spmv_stencil<D, MT, RPT><<<nt, kBlock, 0, s>>>(static_cast<const MT*>(smask), sdict, nstencil, x, xg, y, n_local,
-                                                                std::max<int64_t>(nghost, 0), nt, st, h, hargs, ctx->p2p.dev, shift_on ? 1 : 0,
+                                                                std::max<int64_t>(halo.plan.nghost, 0), nt, st, h, halo.hargs, ctx->p2p.dev, shift_on ? 1 : 0,
                                                                 shift_theta, shift_sigma);
         };
         auto by_rpt = [&](auto mt_tag) {
@@ -473,7 +383,7 @@ template <class D> struct CsrOp : ks_operator {
           auto go = [&](auto un_tag, auto rpt_tag) {
             constexpr int UN = decltype(un_tag)::value, RPT = decltype(rpt_tag)::value;
             const int nt = (int)((n_local + kBlock * RPT - 1) / (kBlock * RPT));
-            ksd::k_spmv_dvi<D, IP, UN, RPT><<<nt, kBlock, 0, s>>>(rp, codes, ddelta, val, x, xg, y, n_local, nt, ndvi, st, hseq, ghost_stride, shift_arg());
+            ksd::k_spmv_dvi<D, IP, UN, RPT><<<nt, kBlock, 0, s>>>(rp, codes, ddelta, val, x, xg, y, n_local, nt, ndvi, st, hseq, halo.ghost_stride, shift_arg());
           };
           using I = std::integral_constant<int, 0>;
           (void)sizeof(I);
@@ -500,10 +410,10 @@ template <class D> struct CsrOp : ks_operator {
             static const int plain_loads = env_int("KS_SELL_PLAIN_LOADS", 0);  // experiment: default-policy loads of the matrix streams
             if (plain_loads)
               ksd::k_spmv_sell<D, IP, VI, UN, false><<<ng, kBlock, 0, s>>>(static_cast<const IP*>(sliceptr), colidx, val, sperm, x, xg, y,
-                                                                           n_local, nslices, ng, st, hseq, ghost_stride, ndict, shift_arg());
+                                                                           n_local, nslices, ng, st, hseq, halo.ghost_stride, ndict, shift_arg());
             else
               ksd::k_spmv_sell<D, IP, VI, UN, true><<<ng, kBlock, 0, s>>>(static_cast<const IP*>(sliceptr), colidx, val, sperm, x, xg, y,
-                                                                          n_local, nslices, ng, st, hseq, ghost_stride, ndict, shift_arg());
+                                                                          n_local, nslices, ng, st, hseq, halo.ghost_stride, ndict, shift_arg());
           };
           auto by_un = [&](auto vi_tag) {
             if (sell_un <= 4) go(vi_tag, std::integral_constant<int, 4>{});
@@ -526,8 +436,8 @@ template <class D> struct CsrOp : ks_operator {
             ksd::HaloFused h = hf;
             h.npush = std::min(h.npush, nblk);
             ksd::k_spmv_csr<D, IP, VI, NI><<<nblk, kBlock, 0, s>>>(static_cast<const IP*>(blkptr), blkrow, static_cast<const IP*>(rowptr), colidx,
-                                                                   val, x, xg, y, n_local, nblk, st, hseq, ghost_stride, ndict, blkpart, lpart,
-                                                                   nullptr, 0, h, hargs, ctx->p2p.dev, csr_nt != 0, row_gather, shift_arg());
+                                                                   val, x, xg, y, n_local, nblk, st, hseq, halo.ghost_stride, ndict, blkpart, lpart,
+                                                                   nullptr, 0, h, halo.hargs, ctx->p2p.dev, csr_nt != 0, row_gather, shift_arg());
           }
           else
             throw KsError{KS_ERR_INTERNAL, "CSR row blocks of " + std::to_string(NI) + " x 256 entries exceed the LDS budget of this element type"};
@@ -651,6 +561,21 @@ void build_csr_host(int64_t nrows, int64_t ncols, int64_t nnz, const void* ptr, 
         vv[q] = v[p];
       }
   }
+}
+
+// ... and of a distributed row block (ks_operator_csr_dist: 0-based, local-extended columns nrows + ghost slot) into the same arrays
+inline void build_csr_dist_host(int64_t nrows, int64_t nghost, int64_t nnz, const int64_t* rowptr, const int32_t* colidx,
+                                std::vector<int64_t>& rp, std::vector<int32_t>& ci) {
+  KS_REQUIRE(nrows < (int64_t)2147483647 && nghost < (int64_t)2147483647 - nrows, KS_ERR_ARGUMENT, "local-extended column range must fit int32");
+  rp.resize(nrows + 1);
+  KS_REQUIRE(rowptr[0] == 0 && rowptr[nrows] == nnz, KS_ERR_ARGUMENT, "row pointer does not match nnz");
+  for (int64_t i = 0; i <= nrows; ++i) {
+    KS_REQUIRE(i == 0 || (rowptr[i] >= rowptr[i - 1] && rowptr[i] <= nnz), KS_ERR_ARGUMENT, "pointer array is not monotone within [0, nnz]");
+    rp[i] = rowptr[i];
+  }
+  ci.assign(colidx, colidx + nnz);
+  for (int64_t p = 0; p < nnz; ++p)
+    KS_REQUIRE(ci[p] >= 0 && ci[p] < nrows + nghost, KS_ERR_ARGUMENT, "local-extended column index out of range");
 }
 
 // device copy of the non-zero offsets in the width the kernels will use

@@ -30,10 +30,11 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "ks_host_defs.hpp"  // kP2pMaxNeigh (the host-only halo plan checks it)
+
 namespace ksd {
 
 constexpr int kP2pMaxRanks = 16;
-constexpr int kP2pMaxNeigh = 16;
 
 struct P2pDev {
   uint64_t* region[kP2pMaxRanks];  // region[q]: rank q's region as mapped HERE (region[rank] is the local one)

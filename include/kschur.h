@@ -668,6 +668,20 @@ int ks_host_csr_plan(int64_t nrows_local, int64_t ncols, int64_t nnz, const void
                      int64_t nghost, int64_t nlow, int* plan_layout, int* ndict, double* bytes_per_nnz,
                      double* aux_bytes, int64_t* facts, int32_t* stencil_delta, int64_t* blkrow, int64_t* blkptr,
                      int64_t blk_cap, int64_t* cb_bounds, int cb_cap);
+/* The halo plan ks_operator_csr_dist would upload for these arguments (the same ones, minus context, values and handle) on rank
+ * `rank` with elements of `elem_size` bytes (8: Float64, 16: ComplexF64), planned on the host: no device is touched, and every
+ * argument check of ks_operator_csr_dist that does not need its context fails here with the same code and message.  Out (each may
+ * be NULL): facts[KS_HALO_NFACTS] indexed by KS_HALO_* -- NLOW: ghost slots owned by lower ranks (-1: a lower-ranked neighbour
+ * is listed after one that is not lower); [GHOST_LO_END, GHOST_HI_BEGIN): the longest run of rows without a ghost column;
+ * NSCATTER: entries that go through the pack kernel --, recv_ptr and pack_ptr (nneigh + 1 entries each), send_first (nneigh
+ * entries; >= 0: the neighbour's send list is this consecutive run and goes out in place), the packed lists (NSCATTER entries, at
+ * most packed_cap are written) and p2p_ghost[2] = {elements between the two ghost slots of the peer-to-peer transport, bytes of
+ * the shared arena they take}; asking for p2p_ghost also applies that transport's limit of 16 neighbours. */
+enum { KS_HALO_NLOW = 0, KS_HALO_GHOST_LO_END, KS_HALO_GHOST_HI_BEGIN, KS_HALO_NSCATTER, KS_HALO_NFACTS };
+int ks_host_halo_plan(int64_t nrows_local, int64_t nghost, int64_t nnz, const int64_t* rowptr, const int32_t* colidx,
+                      int nneigh, const int32_t* neigh, const int64_t* send_ptr, const int32_t* send_idx,
+                      const int64_t* recv_cnt, int rank, int elem_size, int64_t* facts, int64_t* recv_ptr,
+                      int64_t* send_first, int64_t* pack_ptr, int32_t* packed, int64_t packed_cap, int64_t* p2p_ghost);
 /* The matrix that DEFINES ks_operator_grid (mul!(y, A, x), src/expansion.jl:121), as 0-based CSR with ascending columns, without
  * a device: rowptr n + 1 entries, colidx / val `cap` entries.  *nnz (may be NULL) receives the number of stored entries -- the
  * in-grid taps, n + 2 ((nx-1) ny nz + nx (ny-1) nz + nx ny (nz-1)) -- also when the call fails because cap is smaller than that
