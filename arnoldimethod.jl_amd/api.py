@@ -484,9 +484,10 @@ def _grid_radius(radius, periodic, wrap):
     return int(radius)
 
 
-def _grid_args(shape, taps, potential, dtype, radius=1):
+def _grid_args(shape, taps, potential, dtype, radius=1, box=False):
     """(dtype, dims, taps, potential or None) of a grid operator.  The element type is promoted like `_tridiag_args` promotes
-    (ComplexF64 as soon as the taps or the potential are complex) unless `dtype` pins it; a pinned Float64 refuses imaginary parts."""
+    (ComplexF64 as soon as the taps or the potential are complex) unless `dtype` pins it; a pinned Float64 refuses imaginary parts.
+    `box`: the 3^ndim taps of a box stencil, flat or as an array of shape (3,) * ndim in C order."""
     try:
         dims = np.atleast_1d(np.asarray(shape, dtype=np.int64))
     except (TypeError, ValueError, OverflowError) as e:
@@ -501,7 +502,13 @@ def _grid_args(shape, taps, potential, dtype, radius=1):
         raise ArgumentError(f"element type must be float64 or complex128, not {dt}")
     if dt.kind == "f" and cplx and (np.any(t.imag != 0) or (v is not None and np.any(v.imag != 0))):
         raise ArgumentError("taps or potential have an imaginary part but the element type is Float64 (KS_F64)")
-    if t.shape != (2 * ndim * radius + 1,):
+    if box:
+        if t.shape == (3,) * ndim:
+            t = t.reshape(-1)
+        if t.shape != (3 ** ndim,):
+            raise DimensionMismatch(f"the box stencil of a {ndim}-D grid takes {3 ** ndim} taps in ascending column order, flat or of shape "
+                                    f"{(3,) * ndim} ([dz, dy, dx]), got shape {t.shape}")
+    elif t.shape != (2 * ndim * radius + 1,):
         of = "" if radius == 1 else f" of radius {radius}"
         raise DimensionMismatch(f"a {ndim}-D grid{of} takes {2 * ndim * radius + 1} taps in ascending column order, got shape {t.shape}")
     t = np.ascontiguousarray(t.real if dt.kind == "f" else t, dtype=dt)
@@ -693,6 +700,48 @@ def host_grid_variable_matrix(shape, taps, coeff, potential=None, dtype=None):
     n, nnz = _grid_nnz(dims)
     return _host_grid_csr(lib.ks_host_grid_var_matrix, n, nnz, dt, int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data,
                           c.ctypes.data, None if v is None else v.ctypes.data)
+
+
+def _grid_box_nnz(dims):
+    """(n, nnz) of a box-stencil grid matrix, nnz = prod_a (3 m_a - 2); (0, 0) for a shape that the library refuses."""
+    n, _ = _grid_nnz(dims)
+    return n, (math.prod(3 * int(d) - 2 for d in dims) if n else 0)
+
+
+def grid_box_operator(shape, taps, potential=None, dtype=None, ctx: Context | None = None) -> Operator:
+    """Matrix-free operator of a constant-coefficient 3-, 9- or 27-point BOX stencil plus a per-point diagonal term on a grid
+    (`ks_operator_grid_box`): mul!(y, A, x), src/expansion.jl:121, for stencils that link a point to its diagonal neighbours too --
+    the mixed derivatives of -div(D grad) + V with a full constant tensor D (`extras.tensor_laplacian_taps`), compact (Mehrstellen)
+    Laplacians, stiffness and mass matrices of multilinear (Q1) finite elements on a uniform grid (`extras.q1_fem_taps`) -- with
+    nothing stored per non-zero: 24 bytes per row and product in Float64 (16 without a potential) where the stored matrix streams
+    about 330.
+
+    `shape`, `potential`, `dtype`: as for `grid_operator` (open boundaries).  `taps`: 3^ndim values in ascending column order --
+    flat, slot k = 9 (dz + 1) + 3 (dy + 1) + (dx + 1) in 3-D, k = 3 (dy + 1) + (dx + 1) in 2-D, k = dx + 1 in 1-D, or an array of
+    shape (3,) * ndim in C order ([dz, dy, dx], so that `taps.ravel()` is the slot order).  Row r has the entry taps[k] at column
+    r + dx + nx (dy + ny dz) for every slot whose neighbour lies inside the grid (stored even where the tap is zero); the diagonal
+    entry is centre + potential[r].  The operator is exactly the matrix `host_grid_box_matrix` returns, and its products have the
+    bits `csr_operator` of that matrix gives.  Periodic axes, a variable coefficient and a radius above 1 are not offered.
+
+    `operator.grid_info`: shape, taps (flat), has_potential, box=True, bytes_per_row."""
+    ctx = ctx or default_context()
+    lib = _lib.load()
+    dt, dims, t, v = _grid_args(shape, taps, potential, dtype, box=True)
+    h = C.c_void_p()
+    check(lib.ks_operator_grid_box(ctx._h, int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data, None if v is None else v.ctypes.data,
+                                   C.byref(h)))
+    return _grid_operator(ctx, h, dims, dt, t, v, box=True)
+
+
+def host_grid_box_matrix(shape, taps, potential=None, dtype=None):
+    """The matrix that defines `grid_box_operator(shape, taps, potential)` as a scipy.sparse.csr_matrix (`ks_host_grid_box_matrix`:
+    the host path, no device): ascending columns, nnz = prod_a (3 m_a - 2), an entry stored even where its tap is zero, the diagonal
+    entry centre + potential[r].  In 1-D it is the matrix of `host_grid_matrix`."""
+    lib = _lib.load()
+    dt, dims, t, v = _grid_args(shape, taps, potential, dtype, box=True)
+    n, nnz = _grid_box_nnz(dims)
+    return _host_grid_csr(lib.ks_host_grid_box_matrix, n, nnz, dt, int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data,
+                          None if v is None else v.ctypes.data)
 
 
 def host_operator(fn, n: int, dtype=np.float64, ctx: Context | None = None) -> Operator:

@@ -45,6 +45,7 @@ using ksd::kBlock;
 #include "ks_product.hpp"    // product of operators: generalized problems composed in HBM
 #include "ks_grid.hpp"       // matrix-free grid operator: stencil taps in the kernel arguments plus a per-point diagonal
 #include "ks_grid_var.hpp"   // ... with a cell-centred coefficient: the link entries formed in registers from c
+#include "ks_grid_box.hpp"   // ... with the diagonal neighbours: the 9- / 27-point box stencil
 #include "ks_workspace.hpp"  // ks_workspace, launch helpers, expansion, rotations
 #include "ks_block.hpp"      // s-step (block) expansion: launchers, shifts, block sizes
 #include "ks_backend.hpp"    // HipBackend, residual checks, placement search
@@ -52,7 +53,7 @@ using ksd::kBlock;
 
 namespace {
 
-// the guards the four grid operators share; make(D{}, who) builds the operator of element type D
+// the guards the grid operators share; make(D{}, who) builds the operator of element type D
 template <class F> int grid_operator_entry(ks_ctx* ctx, int dtype, ks_operator** out, const std::string& who, F make) {
   return guarded([&] {
     KS_REQUIRE(ctx && out, KS_ERR_ARGUMENT, "null argument");
@@ -63,7 +64,7 @@ template <class F> int grid_operator_entry(ks_ctx* ctx, int dtype, ks_operator**
   });
 }
 
-// the element type of the four host grid matrices: fill(H{}, who) writes the matrix with entries of host type H
+// the element type of the host grid matrices: fill(H{}, who) writes the matrix with entries of host type H
 template <class F> int grid_host_entry(int dtype, const std::string& who, F fill) {
   return guarded([&] {
     KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
@@ -438,6 +439,12 @@ int ks_operator_grid_var(ks_ctx* ctx, int ndim, const int64_t* dims, int dtype, 
                          ks_operator** out) {
   return grid_operator_entry(ctx, dtype, out, "ks_operator_grid_var", [&](auto d, const std::string& who) {
     return make_grid_var<decltype(d)>(ctx, who, ndim, dims, taps, coeff, potential);
+  });
+}
+
+int ks_operator_grid_box(ks_ctx* ctx, int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential, ks_operator** out) {
+  return grid_operator_entry(ctx, dtype, out, "ks_operator_grid_box", [&](auto d, const std::string& who) {
+    return make_grid_box<decltype(d)>(ctx, who, ndim, dims, taps, potential);
   });
 }
 
@@ -1640,6 +1647,13 @@ int ks_host_grid_var_matrix(int ndim, const int64_t* dims, int dtype, const void
                             int64_t* rowptr, int32_t* colidx, void* val, int64_t cap, int64_t* nnz) {
   return grid_host_entry(dtype, "ks_host_grid_var_matrix", [&](auto h, const std::string& who) {
     grid::host_var_matrix_entry<decltype(h)>(who, ndim, dims, taps, coeff, potential, rowptr, colidx, val, cap, nnz);
+  });
+}
+
+int ks_host_grid_box_matrix(int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential, int64_t* rowptr,
+                            int32_t* colidx, void* val, int64_t cap, int64_t* nnz) {
+  return grid_host_entry(dtype, "ks_host_grid_box_matrix", [&](auto h, const std::string& who) {
+    grid::host_box_matrix_entry<decltype(h)>(who, ndim, dims, taps, potential, rowptr, colidx, val, cap, nnz);
   });
 }
 

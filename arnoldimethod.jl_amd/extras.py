@@ -306,3 +306,87 @@ def diffusion_terms(shape, coeff, spacing=1.0, potential=None, boundary="dirichl
                 e = np.where(has, e, 0.0)
             d = d - e
     return taps, (d if v is None else d + v)
+
+
+def _box_spacing(ndim, spacing):
+    """One positive, finite grid spacing per axis in the order of the shape (x[, y[, z]])."""
+    h = np.asarray(spacing, dtype=np.float64)
+    if h.ndim == 0:
+        h = np.full(ndim, float(h))
+    if h.shape != (ndim,):
+        raise api.DimensionMismatch(f"spacing takes a scalar or one value per axis ({ndim}), got shape {h.shape}")
+    if not np.all(np.isfinite(h)) or np.any(h <= 0):
+        raise api.ArgumentError(f"spacing must be positive and finite, got {spacing!r}")
+    return h
+
+
+def tensor_laplacian_taps(D, spacing=1.0, scale=1.0) -> np.ndarray:
+    """The taps of `scale * (-div(D grad))` for a constant symmetric ndim x ndim tensor `D` (axes in the order of the shape:
+    x[, y[, z]]) for `api.grid_box_operator`: 3^ndim Float64 values in slot order, slot 9 (dz + 1) + 3 (dy + 1) + (dx + 1) in 3-D.
+    The two axis neighbours of axis a carry -D_aa / h_a^2 and the centre sum_a 2 D_aa / h_a^2 (second central differences; with a
+    diagonal D these are the taps of `fd_laplacian_taps(ndim, 2)` axis by axis); the mixed term -2 D_ab d_a d_b by central
+    differences lives on the four in-plane corners of the axes a < b: the corner (s_a, s_b), s = -1 or +1, carries
+    -s_a s_b D_ab / (2 h_a h_b).  Every other slot is 0.  `spacing`: the grid spacing h, a scalar or one value per axis.  The matrix
+    of these taps is symmetric; it is positive definite for a positive definite D whose mixed terms are small enough against the
+    diagonal ones for the corner entries not to outweigh the axis entries."""
+    try:
+        d = np.atleast_2d(np.asarray(D, dtype=np.float64))
+    except (TypeError, ValueError) as e:
+        raise api.ArgumentError(f"D must be a real ndim x ndim tensor: {e}") from e
+    if d.ndim != 2 or d.shape[0] != d.shape[1] or not 1 <= d.shape[0] <= 3:
+        raise api.DimensionMismatch(f"D must be an ndim x ndim tensor with ndim = 1, 2 or 3, got shape {d.shape}")
+    if not np.all(np.isfinite(d)):
+        raise api.ArgumentError("D must be finite")
+    if not np.array_equal(d, d.T):
+        raise api.ArgumentError("D must be symmetric")
+    ndim = d.shape[0]
+    h = _box_spacing(ndim, spacing)
+    t = np.zeros((3,) * ndim, dtype=np.float64)   # [dz, dy, dx]: axis a is index ndim - 1 - a
+    centre = (1,) * ndim
+
+    def slot(steps):
+        """the index of the neighbour at the given {axis: step}"""
+        i = list(centre)
+        for a, s in steps.items():
+            i[ndim - 1 - a] += s
+        return tuple(i)
+
+    for a in range(ndim):
+        f = float(scale) * d[a, a] / (h[a] * h[a])
+        t[centre] += f * 2.0
+        t[slot({a: -1})] = t[slot({a: 1})] = f * -1.0
+    for a in range(ndim):
+        for b in range(a + 1, ndim):
+            f = float(scale) * d[a, b] / (2.0 * h[a] * h[b])
+            if f == 0.0:   # (no mixed term: the corners stay +0.0)
+                continue
+            for sa in (-1, 1):
+                for sb in (-1, 1):
+                    t[slot({a: sa, b: sb})] = -sa * sb * f
+    return t.ravel()
+
+
+def q1_fem_taps(ndim, spacing=1.0):
+    """(stiffness_taps, mass_taps) of multilinear (Q1) finite elements on a uniform grid for `api.grid_box_operator`, each 3^ndim
+    Float64 values in slot order: the tensor products of the 1-D element matrices K_a = [-1, 2, -1] / h_a and
+    M_a = h_a [1, 4, 1] / 6,  M = prod_a M_a  and  K = sum_a K_a (x) prod_{b != a} M_b.  With the open truncation of the grid
+    operator these are the stiffness and the consistent mass matrix of the interior nodes under homogeneous Dirichlet conditions
+    (the boundary nodes lie one spacing outside the grid); the generalized problem K x = lambda M x runs in HBM with
+    `product_operator` and `residuals(K, X, lambda, M)`."""
+    if isinstance(ndim, (bool, np.bool_)) or not isinstance(ndim, (int, np.integer)) or not 1 <= int(ndim) <= 3:
+        raise api.ArgumentError(f"a grid has 1, 2 or 3 dimensions (ndim), got {ndim!r}")
+    ndim = int(ndim)
+    h = _box_spacing(ndim, spacing)
+    k1 = [np.array([-1.0, 2.0, -1.0]) / h[a] for a in range(ndim)]
+    m1 = [h[a] * np.array([1.0, 4.0, 1.0]) / 6.0 for a in range(ndim)]
+
+    def outer(parts):
+        """the tensor product with axis ndim - 1 slowest: [dz, dy, dx]"""
+        out = parts[ndim - 1]
+        for a in range(ndim - 2, -1, -1):
+            out = np.multiply.outer(out, parts[a])
+        return out
+
+    mass = outer(m1)
+    stiff = sum(outer([k1[b] if b == a else m1[b] for b in range(ndim)]) for a in range(ndim))
+    return np.ascontiguousarray(stiff).ravel(), np.ascontiguousarray(mass).ravel()

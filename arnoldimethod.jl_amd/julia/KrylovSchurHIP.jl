@@ -46,7 +46,7 @@ using LinearAlgebra, SparseArrays, Random
 import ArnoldiMethod
 import ArnoldiMethod: ArnoldiWorkspace, PartialSchur
 
-export HipContext, HipOperator, HipTridiagonalSolve, HipTridiagonalPencil, HipProduct, HipGridOperator, HipGridVariableOperator, tridiag_info, HipWorkspace, HipBasis, HipColumn, HipColumns, hip_partialschur, hip_partialschur!, hip_partialeigen, set_sstep!, relation_breaks
+export HipContext, HipOperator, HipTridiagonalSolve, HipTridiagonalPencil, HipProduct, HipGridOperator, HipGridVariableOperator, HipGridBoxOperator, tridiag_info, HipWorkspace, HipBasis, HipColumn, HipColumns, hip_partialschur, hip_partialschur!, hip_partialeigen, set_sstep!, relation_breaks
 
 const LIB = get(ENV, "KSCHUR_LIB", joinpath(@__DIR__, "..", "libkschur_hip.so"))
 
@@ -331,6 +331,30 @@ function HipGridVariableOperator(ctx::HipContext, dims::NTuple{N,Integer}, taps:
         check(ccall((:ks_operator_grid_var, LIB), Cint,
                     (Ptr{Cvoid}, Cint, Ptr{Int64}, Cint, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),
                     ctx.h, Cint(N), pointer(d), dtype_code(T), pointer(t), pointer(c), potential === nothing ? C_NULL : pointer(v), r))
+    end
+    _finish_operator(T, r[], n, ctx, nothing)
+end
+
+# ... with the DIAGONAL neighbours (ks_operator_grid_box): the 3-, 9- or 27-point box stencil -- mixed derivatives of -div(D grad) + V with
+# a full constant tensor D, compact Laplacians, Q1 stiffness and mass matrices on a uniform grid -- still nothing stored per non-zero.
+# `taps`: 3^N values, an `Array` of size (3, ..., 3) indexed [dx + 2, dy + 2, dz + 2] (column-major: `vec(taps)` is the slot order
+# 9 (dz + 1) + 3 (dy + 1) + (dx + 1), ascending columns) or that vector; `dims`, `potential` as for HipGridOperator (open boundaries).
+# The products have the bits of the stored matrix with the same entries.
+function HipGridBoxOperator(ctx::HipContext, dims::NTuple{N,Integer}, taps::AbstractArray;
+                            potential::Union{Nothing,AbstractArray} = nothing) where {N}
+    1 <= N <= 3 || throw(ArgumentError("a grid has 1, 2 or 3 dimensions"))
+    T = (eltype(taps) <: Complex || (potential !== nothing && eltype(potential) <: Complex)) ? ComplexF64 : Float64
+    (length(taps) == 3^N && (ndims(taps) == 1 || size(taps) == ntuple(_ -> 3, N))) ||
+        throw(DimensionMismatch("the box stencil of a $(N)-D grid takes $(3^N) taps"))
+    n = prod(Int64.(dims))
+    (potential === nothing || length(potential) == n) || throw(DimensionMismatch("potential must have $(n) entries"))
+    d = Int64[dims...]; t = Vector{T}(vec(taps))
+    v = potential === nothing ? T[] : Vector{T}(vec(potential))
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve d t v begin
+        check(ccall((:ks_operator_grid_box, LIB), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{Int64}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),
+                    ctx.h, Cint(N), pointer(d), dtype_code(T), pointer(t), potential === nothing ? C_NULL : pointer(v), r))
     end
     _finish_operator(T, r[], n, ctx, nothing)
 end

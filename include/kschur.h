@@ -300,6 +300,26 @@ int ks_operator_grid_star(ks_ctx* ctx, int ndim, const int64_t* dims /* ndim ent
 int ks_operator_grid_var(ks_ctx* ctx, int ndim, const int64_t* dims /* ndim entries: nx[, ny[, nz]] */, int dtype,
                          const void* taps /* 2*ndim+1 values of dtype */, const double* coeff /* n values */,
                          const void* potential /* n values of dtype, or NULL */, ks_operator** out);
+/* (xii) ... with the DIAGONAL neighbours: the 3-, 9- or 27-point BOX stencil, a link to every neighbour at distance one in the maximum
+ * norm -- the mixed derivatives of -div(D grad) + V with a full constant tensor D (anisotropic media, effective-mass tensors, a lattice
+ * in sheared coordinates), compact (Mehrstellen) Laplacians, stiffness and mass matrices of multilinear (Q1) finite elements on a uniform
+ * grid -- mul!(y, A, x), src/expansion.jl:121, still with nothing stored per non-zero: 24 bytes per row in Float64 (16 without a
+ * potential), twice that in ComplexF64, where the stored matrix streams about 330.  Grid, row numbering, dims, ndim, dtype and potential
+ * as in (viii), open boundaries.  DEFINITION -- the operator is the matrix ks_host_grid_box_matrix returns:
+ *   taps        3^ndim values of dtype in ascending column order: slot k = 9 (dz + 1) + 3 (dy + 1) + (dx + 1) in 3-D,
+ *               k = 3 (dy + 1) + (dx + 1) in 2-D, k = dx + 1 in 1-D, with dx, dy, dz in -1, 0, 1; the centre is slot (3^ndim - 1) / 2
+ *   row         r = ix + nx (iy + ny iz) has the entry taps[k] at column r + dx + nx (dy + ny dz) for every slot whose neighbour
+ *               (ix + dx, iy + dy, iz + dz) lies inside the grid (nothing wraps), stored even where the tap is zero; slot order is
+ *               ascending column order, the columns being lexicographic in (jz, jy, jx);  nnz = prod_a (3 m_a - 2)
+ *   diagonal    centre + potential[r] as in (viii), stored even where it is zero; potential == NULL: centre
+ *   product     every product A[r, s] x[s] rounded on its own and added to +0.0 in slot order, an absent slot not multiplied at all:
+ *               bit-identical to ks_operator_csr of the matrix.  In 1-D the matrix is that of ks_host_grid_matrix with the same taps
+ * KS_ERR_ARGUMENT as in (viii) ("tap k is not finite" for every one of the 3^ndim).  ks_operator_size reports n and nnz,
+ * ks_operator_format 0 / 0 / -1.  The Newton step of the s-step expansion is one launch of the same kernel, as in (viii).  Periodic
+ * axes, a variable coefficient and a radius above 1 are not offered for this stencil. */
+int ks_operator_grid_box(ks_ctx* ctx, int ndim, const int64_t* dims /* ndim entries: nx[, ny[, nz]] */, int dtype,
+                         const void* taps /* 3^ndim values of dtype */, const void* potential /* n values of dtype, or NULL */,
+                         ks_operator** out);
 int ks_operator_destroy(ks_operator* op);
 int ks_operator_size(const ks_operator* op, int64_t* n_local, int64_t* nnz, int* dtype);
 /* Device layout chosen for a stored matrix at upload (mul!(y, A, x), src/expansion.jl:121; all layouts give bit-identical y):
@@ -705,6 +725,12 @@ int ks_host_grid_matrix_star(int ndim, const int64_t* dims, int radius, int dtyp
  * too small).  With c == 1 the arrays are those of ks_host_grid_matrix.  Same refusals as that operator, except that no context is
  * involved. */
 int ks_host_grid_var_matrix(int ndim, const int64_t* dims, int dtype, const void* taps, const double* coeff, const void* potential,
+                            int64_t* rowptr /* n+1 */, int32_t* colidx, void* val, int64_t cap, int64_t* nnz);
+/* ... and the matrix that DEFINES ks_operator_grid_box (mul!(y, A, x), src/expansion.jl:121): `taps` holds 3^ndim values, every row is a
+ * sub-sequence of the 27 slots (ascending columns), an entry is stored even where its tap is zero, *nnz = prod_a (3 m_a - 2) (also
+ * reported when cap is too small).  In 1-D the arrays are those of ks_host_grid_matrix.  Same refusals as that operator, except that no
+ * context is involved. */
+int ks_host_grid_box_matrix(int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential,
                             int64_t* rowptr /* n+1 */, int32_t* colidx, void* val, int64_t cap, int64_t* nnz);
 /* The plan, the factors and the HOST apply of ks_operator_tridiag_solve without a device (docs/src/index.md:234-259: the
  * factorize / ldiv! pair of the shift-invert recipe): x[:, k] = (T - sigma I)^-1 b[:, k] for nrhs columns (column k at b + k ldb,

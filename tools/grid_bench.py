@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The matrix-free grid operator (ks_operator_grid) against the stored layouts, in the solver's own access pattern:
 
-    python tools/grid_bench.py [--sizes 216,100] [--rounds 7] [--chains 5] [--cycles 20] [--no-solve] [--periodic] [--radius R] [--variable]
+    python tools/grid_bench.py [--sizes 216,100] [--rounds 7] [--chains 5] [--cycles 20] [--no-solve] [--periodic] [--radius R] [--variable] [--box]
                                [--complex [--wide]]
 
 Float64, 7-point -Laplacian (+ a harmonic potential) on m x m x m grids.  Per size, in ONE process:
@@ -26,6 +26,14 @@ Float64, 7-point -Laplacian (+ a harmonic potential) on m x m x m grids.  Per si
                (b) csr_operator(host_grid_variable_matrix(...))    the same matrix stored: the only way to run it without (a)
                (c) grid_variable_operator without a diagonal       24 n bytes
                (d) grid_operator with a potential                  24 n bytes: (a) of the plain run, the constant-coefficient floor
+             and the solve on (a) and (b).
+             --box (ks_operator_grid_box) runs the 27-point box stencil of -div(D grad) + V with a full constant tensor D
+             (extras.tensor_laplacian_taps; 19 of the 27 taps are non-zero, all 27 are stored and multiplied) in the same rounds as
+             the 7-point operator, the floor:
+               (a) grid_box_operator with the potential            24 n bytes
+               (b) csr_operator(host_grid_box_matrix(...))         the same matrix stored: the only way to run it without (a)
+               (c) grid_box_operator without a potential           16 n bytes
+               (d) grid_operator with a potential                  24 n bytes: (a) of the plain run, the 7-point floor
              and the solve on (a) and (b).
              --complex runs the grid operators of the run that the other switches select -- (a) and (c); --periodic: (e) alone;
              --variable: (a), (c), (d) -- in the same rounds with ComplexF64 taps, potential and vectors (twice the bytes; c stays
@@ -134,6 +142,7 @@ def main():
     ap.add_argument("--periodic", action="store_true", help="add (e) the periodic grid operator and (f) its stored matrix")
     ap.add_argument("--radius", type=int, default=None, help="2, 3 or 4: (a), (b), (c) with the star stencil of order 2 R")
     ap.add_argument("--variable", action="store_true", help="the variable-coefficient operator against its stored matrix and the constant-coefficient floor")
+    ap.add_argument("--box", action="store_true", help="the 27-point box operator against its stored matrix and the 7-point floor")
     ap.add_argument("--complex", action="store_true", help="the selected grid operators alone, in ComplexF64: products only")
     ap.add_argument("--wide", action="store_true", help="with --complex: the m^2 x 1 x m grid (one-row tiles)")
     args = ap.parse_args()
@@ -142,6 +151,9 @@ def main():
         return
     if args.wide:
         raise SystemExit("--wide belongs to --complex")
+    if args.box:
+        main_box(args)
+        return
     if args.variable:
         main_variable(args)
         return
@@ -316,6 +328,60 @@ def main_variable(args):
                     rate[name].append(s.cycles(args.cycles))
             out["iterations_per_s"] = {name: stats(v) for name, v in rate.items()}
             out["same_restart_trail"] = runs["a_var_diagonal"].trail == runs["b_stored_variable"].trail
+            out["blocks"] = {name: s.ws.sstep_info["blocks"] for name, s in runs.items()}
+            for s in runs.values():
+                s.ws.close()
+        report(out, prod, m, n, args)
+        for op in ops.values():
+            op.close()
+
+
+TENSOR = np.array([[1.0, 0.3, 0.2], [0.3, 1.5, 0.25], [0.2, 0.25, 2.0]])
+
+
+def main_box(args):
+    """--box: the 27-point box operator of -div(D grad) + V with (a) and without (c) the potential, its stored matrix (b), and the
+    7-point operator with a potential (d) as the floor, in the same rounds; the solve on (a) and (b)."""
+    from arnoldimethod_jl_amd import extras
+
+    if args.periodic or args.radius is not None or args.variable or args.complex:
+        raise SystemExit("--box takes no --periodic, --radius, --variable or --complex")
+    taps = extras.tensor_laplacian_taps(TENSOR)
+    ctx = ks.Context(0)
+    for m in (int(s) for s in args.sizes.split(",")):
+        shape, n = (m, m, m), m ** 3
+        V = ks.matrices.harmonic_potential(shape)
+        t0 = time.perf_counter()
+        A = ks.host_grid_box_matrix(shape, taps, V)
+        ops = {
+            "a_box_potential": ks.grid_box_operator(shape, taps, V, ctx=ctx),
+            "b_stored_box": ks.csr_operator(A, ctx),
+            "c_box_plain": ks.grid_box_operator(shape, taps, ctx=ctx),
+            "d_grid_potential": ks.grid_operator(shape, LAPLACE, V, ctx=ctx),
+        }
+        nnz = A.nnz
+        setup_s = time.perf_counter() - t0
+        del A
+        fmt = {"b_stored_box": ops["b_stored_box"].format}
+        by = {"a_box_potential": 24.0 * n, "c_box_plain": 16.0 * n, "d_grid_potential": 24.0 * n,
+              "b_stored_box": fmt["b_stored_box"]["bytes_per_nnz"] * nnz + 16.0 * n}
+        out = dict(m=m, n=n, box=True, nnz=nnz, setup_seconds=round(setup_s, 2), formats=fmt, chains=args.chains, products_per_round=args.chains * MAXDIM)
+        prod = bench_products(ctx, ops, n, args.rounds, args.chains)
+        for name, s in prod.items():
+            s["bytes_per_product"] = by[name]
+            s["hbm_fraction_at_mean"] = by[name] / (s["mean"] * 1e-6) / PEAK
+            s["hbm_fraction_of_kernels"] = by[name] / (s["event_us"] * 1e-6) / PEAK
+        out["us_per_product"] = prod
+        if not args.no_solve:
+            runs = {name: Solve(ctx, ops[name], n) for name in ("a_box_potential", "b_stored_box")}
+            for s in runs.values():
+                s.cycles(3)
+            rate = {name: [] for name in runs}
+            for _ in range(max(3, args.rounds // 2)):
+                for name, s in runs.items():
+                    rate[name].append(s.cycles(args.cycles))
+            out["iterations_per_s"] = {name: stats(v) for name, v in rate.items()}
+            out["same_restart_trail"] = runs["a_box_potential"].trail == runs["b_stored_box"].trail
             out["blocks"] = {name: s.ws.sstep_info["blocks"] for name, s in runs.items()}
             for s in runs.values():
                 s.ws.close()
