@@ -664,13 +664,13 @@ def _grid_coeff(dims, coeff):
         raise ArgumentError(f"coeff must hold real numbers: {e}") from e
 
 
-def grid_variable_operator(shape, taps, coeff, potential=None, dtype=None, ctx: Context | None = None) -> Operator:
+def grid_variable_operator(shape, taps, coeff, potential=None, dtype=None, ctx: Context | None = None, periodic=None, wrap=None) -> Operator:
     """Matrix-free operator of a 3-, 5- or 7-point stencil with a VARIABLE, cell-centred coefficient plus a per-point diagonal
     term on a grid (`ks_operator_grid_var`): mul!(y, A, x), src/expansion.jl:121, for A = -div(c(x) grad) + V(x) and its kin --
     heterogeneous diffusion, a position-dependent effective mass, div (1 / eps) grad -- with nothing stored per non-zero: 32 bytes
     per row and product in Float64 (24 without a potential) where the stored matrix streams about 100.
 
-    `shape`, `taps`, `potential`, `dtype`: as for `grid_operator` (open boundaries, radius 1).  `coeff`: n real values, one per
+    `shape`, `taps`, `potential`, `dtype`: as for `grid_operator` (radius 1).  `coeff`: n real values, one per
     grid point -- flat in row order, or an array of shape (nz, ny, nx) / (ny, nx) in C order; always Float64, also for ComplexF64
     operators.  The entry of the link from row r to its in-grid neighbour s in direction k is fl(0.5 taps[k] * fl(c[r] + c[s]));
     the diagonal entry is centre + potential[r].  The operator is exactly the matrix `host_grid_variable_matrix` returns, and its
@@ -679,27 +679,50 @@ def grid_variable_operator(shape, taps, coeff, potential=None, dtype=None, ctx: 
     The diffusion operator -div(c grad) + V:  `taps, diagonal = extras.diffusion_terms(shape, coeff, spacing, V, boundary)`, then
     `grid_variable_operator(shape, taps, coeff, potential=diagonal)`.
 
-    `operator.grid_info`: shape, taps, has_potential, variable=True, bytes_per_row."""
+    `periodic`, `wrap` (`ks_operator_grid_var_periodic`): as for `grid_operator` -- photonic and phononic crystals, a superlattice
+    with a position-dependent mass, diffusion on a torus.  A link that crosses the boundary of a periodic axis (extent >= 3) carries
+    fl(0.5 wrap[k] * fl(c[r] + c[s])) with s the wrap image at the other end of the line; a row is summed in the 13-slot order of
+    the periodic `grid_operator`.  A complex `wrap` promotes the element type to ComplexF64 (`coeff` stays real); the traffic per row
+    is unchanged.  A band structure at the k-point theta:  `taps, diagonal = extras.diffusion_terms(shape, coeff, spacing, V,
+    periodic=True)`, then `grid_variable_operator(shape, taps, coeff, diagonal, periodic=True, wrap=extras.bloch_wrap(taps, theta))`
+    -- exactly Hermitian.
+
+    `operator.grid_info`: shape, taps, has_potential, variable=True, bytes_per_row, and with `periodic` or `wrap` given also
+    periodic, wrap (as for `grid_operator`)."""
     ctx = ctx or default_context()
     lib = _lib.load()
     dt, dims, t, v = _grid_args(shape, taps, potential, dtype)
     c = _grid_coeff(dims, coeff)
     h = C.c_void_p()
-    check(lib.ks_operator_grid_var(ctx._h, int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data, c.ctypes.data,
-                                   None if v is None else v.ctypes.data, C.byref(h)))
-    return _grid_operator(ctx, h, dims, dt, t, v, extra_bytes=8, variable=True)
+    if periodic is None and wrap is None:
+        check(lib.ks_operator_grid_var(ctx._h, int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data, c.ctypes.data,
+                                       None if v is None else v.ctypes.data, C.byref(h)))
+        return _grid_operator(ctx, h, dims, dt, t, v, extra_bytes=8, variable=True)
+    dt, t, v, flags, w = _grid_wrap_args(dims, t, v, dt, dtype, periodic, wrap)
+    check(lib.ks_operator_grid_var_periodic(ctx._h, int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data, c.ctypes.data,
+                                            None if v is None else v.ctypes.data, flags.ctypes.data, None if w is None else w.ctypes.data,
+                                            C.byref(h)))
+    return _grid_operator(ctx, h, dims, dt, t, v, extra_bytes=8, variable=True, periodic=tuple(bool(f) for f in flags),
+                          wrap=None if w is None else w.copy())
 
 
-def host_grid_variable_matrix(shape, taps, coeff, potential=None, dtype=None):
+def host_grid_variable_matrix(shape, taps, coeff, potential=None, dtype=None, periodic=None, wrap=None):
     """The matrix that defines `grid_variable_operator(shape, taps, coeff, potential)` as a scipy.sparse.csr_matrix
     (`ks_host_grid_var_matrix`: the host path, no device): ascending columns, off-diagonal entries fl(0.5 taps[k] * fl(c[r] + c[s])),
-    the diagonal entry centre + potential[r] stored even where it is zero."""
+    the diagonal entry centre + potential[r] stored even where it is zero.  `periodic`, `wrap`: as for `grid_variable_operator`
+    (`ks_host_grid_var_matrix_periodic`)."""
     lib = _lib.load()
     dt, dims, t, v = _grid_args(shape, taps, potential, dtype)
     c = _grid_coeff(dims, coeff)
-    n, nnz = _grid_nnz(dims)
-    return _host_grid_csr(lib.ks_host_grid_var_matrix, n, nnz, dt, int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data,
-                          c.ctypes.data, None if v is None else v.ctypes.data)
+    head = (int(dims.size), dims.ctypes.data)
+    if periodic is None and wrap is None:
+        n, nnz = _grid_nnz(dims)
+        return _host_grid_csr(lib.ks_host_grid_var_matrix, n, nnz, dt, *head, _dtype_code(dt), t.ctypes.data, c.ctypes.data,
+                              None if v is None else v.ctypes.data)
+    dt, t, v, flags, w = _grid_wrap_args(dims, t, v, dt, dtype, periodic, wrap)
+    n, nnz = _grid_nnz(dims, 1, flags)
+    return _host_grid_csr(lib.ks_host_grid_var_matrix_periodic, n, nnz, dt, *head, _dtype_code(dt), t.ctypes.data, c.ctypes.data,
+                          None if v is None else v.ctypes.data, flags.ctypes.data, None if w is None else w.ctypes.data)
 
 
 def _grid_box_nnz(dims):

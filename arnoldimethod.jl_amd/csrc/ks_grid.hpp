@@ -3,7 +3,7 @@
 // kernel arguments, the only per-row datum is the diagonal entry centre + potential[r] (formed once on the host at upload, by the
 // code that the host matrix runs).  This file: what every grid kernel shares, then the constant-coefficient operators (k_grid: 3-, 5-
 // or 7-point stencil with open or periodic boundaries, ks_operator_grid / ks_operator_grid_periodic; k_grid_star: star stencils of
-// radius 2, 3, 4, ks_operator_grid_star).  ks_grid_var.hpp: the variable-coefficient operator (k_grid_var).
+// radius 2, 3, 4, ks_operator_grid_star).  ks_grid_var.hpp: the variable-coefficient operator (k_grid_var; open or periodic boundaries).
 // Part of the ONE translation unit of libkschur_hip.so: included by ks_hip.hip after ks_tridiag.hpp.
 //
 // An operator IS the matrix its ks_host_grid_* entry returns: the kernel rounds every product on its own and adds the products of a
@@ -64,7 +64,7 @@ template <class T> struct GridDev : GridGeom {
 };
 // ... with periodic axes: the entries of the links that cross the cell boundary and the axes that wrap
 template <class T> struct GridPerDev : GridDev<T> {
-  T wrap[6] = {};         // -z, -y, -x, +x, +y, +z
+  T wrap[6] = {};         // -z, -y, -x, +x, +y, +z (k_grid_var: the HALF wrap values)
   int px = 0, py = 0, pz = 0;
 };
 template <class T, int R> struct GridStarDev : GridGeom {

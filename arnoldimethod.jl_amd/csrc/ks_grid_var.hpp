@@ -11,6 +11,10 @@
 //
 // The operator IS the matrix ks_host_grid_var_matrix returns: the kernel forms every entry by exactly these two roundings (open
 // boundaries, slots -z, -y, -x, centre, +x, +y, +z).
+// With periodic axes (ks_operator_grid_var_periodic, (xi-b): photonic crystals, a superlattice with a position-dependent mass, diffusion
+// on a torus) it is the matrix of ks_host_grid_var_matrix_periodic: a link that crosses the boundary of a periodic axis carries
+// fl(hw_k * fl(c[r] + c[s])), hw_k = 0.5 * wrap_k, s the wrap image at the other end of the line, and a row is summed in the 13-slot
+// order of (ix).  Periodicity is a compile-time variant of the one kernel, as for k_grid; the open instantiation is the kernel as it was.
 //
 // k_grid_var (R = 1).  c travels exactly like x: registers for the planes z - 1, z, z + 1 (the +-z links need c of the planes
 // z +- 1) and z + 2 in flight, an LDS tile of its own beside that of x, the halo cell of both, from which the +-x and +-y links
@@ -37,11 +41,21 @@ __device__ __forceinline__ cd var_entry(cd h, double m) {
 }
 
 // g.tap: the six off-diagonal slots hold the HALF taps h_k, slot 3 the centre.  c: the n coefficients.
-template <class T, int TX, int TY>
+// G = GridPerDev<T>: periodic axes (ks_operator_grid_var_periodic, include/kschur.h (xi-b)), the variant k_grid has: g.wrap holds the
+// HALF wrap values hw_k, a row is summed in the 13-slot order of (ix), and c wraps wherever x wraps -- the halo cell one step
+// outside the grid, the owned point gx = nx / gy = ny of a partial last tile (never stored, its diagonal never loaded), plane -1 and
+// plane nz.  No per-point state is added to the open form's: a link of a point in the grid wraps exactly where the interior link of
+// its direction is absent (in && !hxm: gx == 0, ...), and off[] is the offset the point is LOADED from, negative for a point that is
+// not loaded -- stores and diagonal loads use it only under in[], where it is the point's own offset.  The row of a point is
+// instantiated twice in the periodic form, with and without the two z-wrap links, and a uniform branch per plane picks one: only
+// plane 0 and plane nz - 1 have them, and with them in the one row every plane would keep x and c of plane z - 1 to the end of its
+// rows (DESIGN.md has the register counts of each form).
+template <class T, int TX, int TY, class G>
 __global__ void __launch_bounds__(kBlock)
-    k_grid_var(const GridDev<T> g, const T* __restrict__ x, const double* __restrict__ c, const T* __restrict__ diag,
+    k_grid_var(const G g, const T* __restrict__ x, const double* __restrict__ c, const T* __restrict__ diag,
                T* __restrict__ y, const DevState* __restrict__ st, int shifted, T theta, double sigma) {
   if (st && st->breakdown >= 0) return;
+  constexpr bool PER = !std::is_same<G, GridDev<T>>::value;
   using L = GridLds<TX, TY, 1>;
   constexpr int PPT = L::PPT, HY = L::HY, LW = L::LW;
   static_assert(L::NH == 1, "at most one halo cell per thread");
@@ -61,6 +75,10 @@ __global__ void __launch_bounds__(kBlock)
     int gx, gy;
     grid_owned<TX, TY, 1>(g, it, tid + k * kBlock, gx, gy, in[k], off[k], li[k]);
     grid_neighbours(g, gx, gy, in[k], hxm[k], hxp[k], hym[k], hyp[k]);
+    if constexpr (PER) {
+      const bool ix = g.px && gx == g.nx && gy < g.ny, iy = g.py && gy == g.ny && gx < g.nx;   // the image of [0, gy] / of [gx, 0]
+      off[k] = in[k] ? off[k] : ix ? (int64_t)gy * g.nx : iy ? (int64_t)gx : (int64_t)-1;
+    }
   }
   // this thread's halo cell: left column, right column, row below, row above
   bool hin = false;
@@ -72,13 +90,29 @@ __global__ void __launch_bounds__(kBlock)
     else if (tid < 2 * TY) { hx = TX; hy = tid - TY; }
     else if (tid < 2 * TY + TX) { hx = tid - 2 * TY; hy = -1; }
     else { hx = tid - 2 * TY - TX; hy = TY; }
-    const int gx = it.x0 + hx, gy = it.y0 + hy;
+    int gx = it.x0 + hx, gy = it.y0 + hy;
+    if constexpr (PER) {
+      if (g.px) gx = gx == -1 ? g.nx - 1 : gx == g.nx ? 0 : gx;
+      if (g.py) gy = gy == -1 ? g.ny - 1 : gy == g.ny ? 0 : gy;
+    }
     hin = gx >= 0 && gx < g.nx && gy >= 0 && gy < g.ny;
     hoff = (int64_t)gy * g.nx + gx;
     hli = (hy + HY) * LW + hx + 1;
   }
-  auto ldx = [&](int z, int64_t o, bool ok) { return ok && z >= 0 && z < g.nz ? x[(int64_t)z * P + o] : zero_of(T{}); };
-  auto ldc = [&](int z, int64_t o, bool ok) { return ok && z >= 0 && z < g.nz ? c[(int64_t)z * P + o] : 0.0; };
+  // periodic in z: plane -1 is plane nz - 1, plane nz is plane 0 (z is never further out than one plane)
+  auto pl = [&](int z) {
+    if constexpr (PER) {
+      if (g.pz) z = z < 0 ? g.nz - 1 : z >= g.nz ? 0 : z;
+    }
+    return z;
+  };
+  auto ldx = [&](int z, int64_t o, bool ok) { z = pl(z); return ok && z >= 0 && z < g.nz ? x[(int64_t)z * P + o] : zero_of(T{}); };
+  auto ldc = [&](int z, int64_t o, bool ok) { z = pl(z); return ok && z >= 0 && z < g.nz ? c[(int64_t)z * P + o] : 0.0; };
+  // the owned point k is LOADED: with periodic axes also the wrap images beyond a partial last tile
+  auto lk = [&](int k) {
+    if constexpr (PER) return off[k] >= 0;
+    else return in[k];
+  };
 
   // Register sets: xr[0..3] / cr[0..3] hold the owned points of four consecutive planes and rotate by NAME (the z-loop is
   // unrolled by four); hr / hc [0..1]: this thread's halo cell of the planes of even / odd steps, dr[0..1]: the diagonal.
@@ -90,12 +124,12 @@ __global__ void __launch_bounds__(kBlock)
   hc[1] = ldc(za + 1, hoff, hin && za + 1 < zb);
 #pragma unroll
   for (int k = 0; k < PPT; ++k) {
-    xr[0][k] = ldx(za - 1, off[k], in[k]);
-    xr[1][k] = ldx(za, off[k], in[k]);
-    xr[2][k] = ldx(za + 1, off[k], in[k]);
-    cr[0][k] = ldc(za - 1, off[k], in[k]);
-    cr[1][k] = ldc(za, off[k], in[k]);
-    cr[2][k] = ldc(za + 1, off[k], in[k]);
+    xr[0][k] = ldx(za - 1, off[k], lk(k));
+    xr[1][k] = ldx(za, off[k], lk(k));
+    xr[2][k] = ldx(za + 1, off[k], lk(k));
+    cr[0][k] = ldc(za - 1, off[k], lk(k));
+    cr[1][k] = ldc(za, off[k], lk(k));
+    cr[2][k] = ldc(za + 1, off[k], lk(k));
     dr[0][k] = diag ? grid_ldd(diag, g, P, za, off[k], in[k]) : g.tap[3];
     dr[1][k] = dr[0][k];
   }
@@ -117,29 +151,60 @@ __global__ void __launch_bounds__(kBlock)
     hcw = ldc(z + 2, hoff, hin && z + 2 < zb);
 #pragma unroll
     for (int k = 0; k < PPT; ++k) {
-      xn[k] = ldx(z + 2, off[k], in[k] && z + 2 <= zb);   // (plane zb is the +z link of the range's last plane)
-      cn[k] = ldc(z + 2, off[k], in[k] && z + 2 <= zb);
+      xn[k] = ldx(z + 2, off[k], lk(k) && z + 2 <= zb);   // (plane zb is the +z link of the range's last plane)
+      cn[k] = ldc(z + 2, off[k], lk(k) && z + 2 <= zb);
       if (diag) dn[k] = grid_ldd(diag, g, P, z + 1, off[k], in[k] && z + 1 < zb);
     }
     __syncthreads();
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
+    // the row of point k; ZW: this plane has a z-wrap link (periodic form, plane 0 or nz - 1)
+    auto row = [&](int k, auto zwc) {
+      [[maybe_unused]] constexpr bool ZW = decltype(zwc)::value;
       T s = zero_of(T{});
       const double cr_ = cc[k];
       // a link: entry = h (c_r + c_s), the sum rounded, then the product(s); then the entry times x_s, rounded on its own
       auto link = [&](const T& h, double cs, const T& xs) { return add_(s, mul_nc(var_entry(h, cr_ + cs), xs)); };
+      if constexpr (PER) {
+        if (ZW && z + 1 == g.nz) s = link(g.wrap[5], cp[k], xp[k]);
+      }
       if (z > 0) s = link(g.tap[0], cm[k], xm[k]);
       if constexpr (HY) {
+        if constexpr (PER) {
+          if (g.py && in[k] && !hyp[k]) s = link(g.wrap[4], cl[li[k] + LW], tl[li[k] + LW]);
+        }
         if (hym[k]) s = link(g.tap[1], cl[li[k] - LW], tl[li[k] - LW]);
+      }
+      if constexpr (PER) {
+        if (g.px && in[k] && !hxp[k]) s = link(g.wrap[3], cl[li[k] + 1], tl[li[k] + 1]);
       }
       if (hxm[k]) s = link(g.tap[2], cl[li[k] - 1], tl[li[k] - 1]);
       s = add_(s, mul_nc(dc[k], xc[k]));
       if (hxp[k]) s = link(g.tap[4], cl[li[k] + 1], tl[li[k] + 1]);
+      if constexpr (PER) {
+        if (g.px && in[k] && !hxm[k]) s = link(g.wrap[2], cl[li[k] - 1], tl[li[k] - 1]);
+      }
       if constexpr (HY) {
         if (hyp[k]) s = link(g.tap[5], cl[li[k] + LW], tl[li[k] + LW]);
+        if constexpr (PER) {
+          if (g.py && in[k] && !hym[k]) s = link(g.wrap[1], cl[li[k] - LW], tl[li[k] - LW]);
+        }
       }
       if (z + 1 < g.nz) s = link(g.tap[6], cp[k], xp[k]);
+      if constexpr (PER) {
+        if (ZW && z == 0) s = link(g.wrap[0], cm[k], xm[k]);
+      }
       store(z, off[k], in[k], s, xc[k]);
+    };
+    if constexpr (PER) {
+      if (g.pz && (z == 0 || z + 1 == g.nz)) {
+#pragma unroll
+        for (int k = 0; k < PPT; ++k) row(k, std::true_type{});
+      } else {
+#pragma unroll
+        for (int k = 0; k < PPT; ++k) row(k, std::false_type{});
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < PPT; ++k) row(k, std::false_type{});
     }
   };
   // (the exits are uniform over the workgroup: the barriers match)
@@ -185,19 +250,26 @@ Shape check_var(const std::string& who, int ndim, const int64_t* dims, const voi
   return s;
 }
 
-// the host entry point (ks_host_grid_var_matrix, include/kschur.h (xi)): the checks, then the open radius-1 rows with the entry
-// of every link formed from the coefficient
+// the six wrap values halved like the taps: hw_k = 0.5 wrap_k (-z, -y, -x, +x, +y, +z; an axis that does not wrap: zero, never used)
+template <class H> void half_wrap(const Wrap<H>& W, H (&out)[6]) {
+  for (int k = 0; k < 6; ++k) out[k] = half_tap(W.w[k]);
+}
+
+// both host entry points (ks_host_grid_var_matrix, ks_host_grid_var_matrix_periodic, include/kschur.h (xi), (xi-b)): the checks, then
+// the radius-1 rows with the entry of every link formed from the coefficient -- a link that crosses the boundary of a periodic axis
+// from the half wrap value of its direction and the coefficient of the wrap image
 template <class H>
 void host_var_matrix_entry(const std::string& who, int ndim, const int64_t* dims, const void* taps, const double* coeff, const void* pot,
-                           int64_t* rowptr, int32_t* colidx, void* val, int64_t cap, int64_t* nnz) {
-  const Shape s = check_var<H>(who, ndim, dims, taps, coeff, pot);
+                           const int* periodic, const void* wrap, int64_t* rowptr, int32_t* colidx, void* val, int64_t cap, int64_t* nnz) {
+  Shape s = check_var<H>(who, ndim, dims, taps, coeff, pot);
+  const Wrap<H> W = check_wrap<H>(who, s, ndim, taps, periodic, wrap);
   csr_begin(who, s, rowptr, colidx, static_cast<H*>(val), cap, nnz);
-  H h[7];
+  H h[7], hw[6];
   half_taps(ndim, static_cast<const H*>(taps), h);
-  const bool open[3] = {false, false, false};
-  seven_slot_rows(s, open, h[3], static_cast<const H*>(pot), rowptr, colidx, static_cast<H*>(val), [&](int k, int64_t r, int64_t c, bool) {
+  half_wrap(W, hw);
+  seven_slot_rows(s, W.per, h[3], static_cast<const H*>(pot), rowptr, colidx, static_cast<H*>(val), [&](int k, int64_t r, int64_t c, bool wrapped) {
     const double m = coeff[r] + coeff[c];
-    return var_entry(h[k], m);
+    return var_entry(wrapped ? hw[k - (k > 3)] : h[k], m);
   });
 }
 
@@ -205,25 +277,37 @@ void host_var_matrix_entry(const std::string& who, int ndim, const int64_t* dims
 
 template <class D> struct VarGridOp : GridOpBase<D> {
   using GridOpBase<D>::ctx; using GridOpBase<D>::diag; using GridOpBase<D>::nitems; using GridOpBase<D>::wide;
-  ksd::GridDev<D> g{};       // (tap: the half taps)
+  ksd::GridPerDev<D> g{};    // (tap: the half taps, wrap: the half wrap values; the open operator's kernel takes its GridDev part)
+  bool periodic = false;     // some axis wraps: the kernel's periodic instantiation
   double* coeff = nullptr;   // c[r], always Float64
   ~VarGridOp() override { (void)hipFree(coeff); }
   void launch(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma) override {
     using TL = ksd::GridTileOf<D, 1, true>;
-    if (wide) ksd::k_grid_var<D, TL::WX, 1><<<nitems, kBlock, 0, ctx->stream>>>(g, x, coeff, diag, y, st, shifted, theta, sigma);
-    else ksd::k_grid_var<D, TL::TX, TL::TY><<<nitems, kBlock, 0, ctx->stream>>>(g, x, coeff, diag, y, st, shifted, theta, sigma);
+    using GP = ksd::GridPerDev<D>;
+    using GO = ksd::GridDev<D>;
+    const GO& go = g;
+    if (periodic) {
+      if (wide) ksd::k_grid_var<D, TL::WX, 1, GP><<<nitems, kBlock, 0, ctx->stream>>>(g, x, coeff, diag, y, st, shifted, theta, sigma);
+      else ksd::k_grid_var<D, TL::TX, TL::TY, GP><<<nitems, kBlock, 0, ctx->stream>>>(g, x, coeff, diag, y, st, shifted, theta, sigma);
+    } else if (wide) ksd::k_grid_var<D, TL::WX, 1, GO><<<nitems, kBlock, 0, ctx->stream>>>(go, x, coeff, diag, y, st, shifted, theta, sigma);
+    else ksd::k_grid_var<D, TL::TX, TL::TY, GO><<<nitems, kBlock, 0, ctx->stream>>>(go, x, coeff, diag, y, st, shifted, theta, sigma);
   }
 };
 
 template <class D>
 ks_operator* make_grid_var(ks_ctx* ctx, const std::string& who, int ndim, const int64_t* dims, const void* taps, const double* coeff,
-                           const void* potential) {
+                           const void* potential, const int* periodic, const void* wrap) {
   using H = typename HostT<D>::type;
-  const grid::Shape s = grid::check_var<H>(who, ndim, dims, taps, coeff, potential);
+  grid::Shape s = grid::check_var<H>(who, ndim, dims, taps, coeff, potential);
+  const grid::Wrap<H> W = grid::check_wrap<H>(who, s, ndim, taps, periodic, wrap);
   auto op = std::make_unique<VarGridOp<D>>();
-  H h[7];
+  H h[7], hw[6];
   grid::half_taps(ndim, static_cast<const H*>(taps), h);
+  grid::half_wrap(W, hw);
   std::memcpy(op->g.tap, h, sizeof(h));
+  std::memcpy(op->g.wrap, hw, sizeof(hw));
+  op->g.px = W.per[0]; op->g.py = W.per[1]; op->g.pz = W.per[2];
+  op->periodic = W.any();
   op->init(ctx, who, s, 1, true, op->g);
   KS_HIP(hipMalloc(&op->coeff, (size_t)s.n * sizeof(double)));
   KS_HIP(hipMemcpy(op->coeff, coeff, (size_t)s.n * sizeof(double), hipMemcpyHostToDevice));

@@ -438,7 +438,14 @@ int ks_operator_grid_periodic(ks_ctx* ctx, int ndim, const int64_t* dims, int dt
 int ks_operator_grid_var(ks_ctx* ctx, int ndim, const int64_t* dims, int dtype, const void* taps, const double* coeff, const void* potential,
                          ks_operator** out) {
   return grid_operator_entry(ctx, dtype, out, "ks_operator_grid_var", [&](auto d, const std::string& who) {
-    return make_grid_var<decltype(d)>(ctx, who, ndim, dims, taps, coeff, potential);
+    return make_grid_var<decltype(d)>(ctx, who, ndim, dims, taps, coeff, potential, nullptr, nullptr);
+  });
+}
+
+int ks_operator_grid_var_periodic(ks_ctx* ctx, int ndim, const int64_t* dims, int dtype, const void* taps, const double* coeff,
+                                  const void* potential, const int* periodic, const void* wrap, ks_operator** out) {
+  return grid_operator_entry(ctx, dtype, out, "ks_operator_grid_var_periodic", [&](auto d, const std::string& who) {
+    return make_grid_var<decltype(d)>(ctx, who, ndim, dims, taps, coeff, potential, periodic, wrap);
   });
 }
 
@@ -1646,7 +1653,15 @@ int ks_host_grid_matrix_periodic(int ndim, const int64_t* dims, int dtype, const
 int ks_host_grid_var_matrix(int ndim, const int64_t* dims, int dtype, const void* taps, const double* coeff, const void* potential,
                             int64_t* rowptr, int32_t* colidx, void* val, int64_t cap, int64_t* nnz) {
   return grid_host_entry(dtype, "ks_host_grid_var_matrix", [&](auto h, const std::string& who) {
-    grid::host_var_matrix_entry<decltype(h)>(who, ndim, dims, taps, coeff, potential, rowptr, colidx, val, cap, nnz);
+    grid::host_var_matrix_entry<decltype(h)>(who, ndim, dims, taps, coeff, potential, nullptr, nullptr, rowptr, colidx, val, cap, nnz);
+  });
+}
+
+int ks_host_grid_var_matrix_periodic(int ndim, const int64_t* dims, int dtype, const void* taps, const double* coeff,
+                                     const void* potential, const int* periodic, const void* wrap, int64_t* rowptr, int32_t* colidx,
+                                     void* val, int64_t cap, int64_t* nnz) {
+  return grid_host_entry(dtype, "ks_host_grid_var_matrix_periodic", [&](auto h, const std::string& who) {
+    grid::host_var_matrix_entry<decltype(h)>(who, ndim, dims, taps, coeff, potential, periodic, wrap, rowptr, colidx, val, cap, nnz);
   });
 }
 

@@ -206,7 +206,15 @@ def bloch_wrap(taps, theta) -> np.ndarray:
     cell in the + direction of axis a carries t_{+a} e^{+i theta_a}, the one in the - direction t_{-a} e^{-i theta_a} (a band
     structure at the k-point theta_a = k_a L_a).  `taps`: the 2 ndim + 1 taps in ascending column order; `theta`: one phase per axis
     in the order of the shape (x[, y[, z]]).  Returns 2 ndim complex values in the order of the taps without the centre.  With
-    symmetric real taps (or t_{-a} = conj(t_{+a})) the operator is Hermitian."""
+    symmetric real taps (or t_{-a} = conj(t_{+a})) the operator is Hermitian.
+
+    The same array serves `api.grid_variable_operator`: a crystal with a variable coefficient (div (1 / eps) grad, a
+    position-dependent mass) at the k-point theta is
+
+        taps, diagonal = diffusion_terms(shape, coeff, spacing, V, periodic=True)
+        op = api.grid_variable_operator(shape, taps, coeff, diagonal, periodic=True, wrap=bloch_wrap(taps, theta))
+
+    -- exactly Hermitian for a real `coeff`; the diagonal does not depend on theta (|hw| = |h|)."""
     t = np.asarray(taps)
     th = np.atleast_1d(np.asarray(theta, dtype=np.float64))
     if t.ndim != 1 or t.size not in (3, 5, 7):
@@ -261,7 +269,7 @@ def fd_laplacian_taps(ndim, order, spacing=1.0, scale=1.0) -> np.ndarray:
     return t
 
 
-def diffusion_terms(shape, coeff, spacing=1.0, potential=None, boundary="dirichlet"):
+def diffusion_terms(shape, coeff, spacing=1.0, potential=None, boundary="dirichlet", periodic=None):
     """(taps, diagonal) of the diffusion operator -div(c grad) + V on a grid with the cell-centred coefficient `coeff`, for
     `api.grid_variable_operator`:
 
@@ -273,8 +281,13 @@ def diffusion_terms(shape, coeff, spacing=1.0, potential=None, boundary="dirichl
     arithmetic mean of the two coefficients over h^2.  `diagonal[r] = (0.0 - e_1 - e_2 ...) + V[r]`, the e_k of the row in slot order
     (-z, -y, -x, +x, +y, +z), flat in row order.  A direction whose neighbour lies outside the grid: `boundary="dirichlet"` takes
     c[s] := c[r] (a ghost cell with the boundary cell's coefficient and the value 0: with c == 1 and spacing 1 exactly the
-    [-1 ... 2 ndim ... -1] Laplacian), `"neumann"` leaves the term out (no flux: the row sums vanish up to rounding).  Plain numpy,
-    no device."""
+    [-1 ... 2 ndim ... -1] Laplacian), `"neumann"` leaves the term out (no flux: the row sums vanish up to rounding).
+
+    `periodic`: True, or one bool per axis in the order of the shape, for `api.grid_variable_operator(..., periodic=periodic)`: on
+    such an axis (extent >= 3) the neighbour beyond the edge is the wrap image at the other end of the line, its c[s] enters the
+    link's e, and e is subtracted in the diagonal like that of an interior link (on a torus the row sums vanish up to rounding);
+    `boundary` applies to the remaining open axes.  The diagonal does not depend on a Bloch phase (|hw| = |h|): for a k-point pass
+    `wrap=bloch_wrap(taps, theta)` to the operator and keep this diagonal.  Plain numpy, no device."""
     if boundary not in ("dirichlet", "neumann"):
         raise api.ArgumentError(f"boundary must be 'dirichlet' or 'neumann', got {boundary!r}")
     try:
@@ -289,6 +302,11 @@ def diffusion_terms(shape, coeff, spacing=1.0, potential=None, boundary="dirichl
     if np.any(dims < 1):
         raise api.ArgumentError(f"every extent must be at least 1, shape = {shape!r}")
     c = api._grid_coeff(dims, coeff)
+    per = [bool(f) for f in api._grid_wrap_args(dims, _t, v, _dt, None, periodic, None)[3]]
+    for a in range(ndim):
+        if per[a] and dims[a] < 3:   # (the library's wording: ks_operator_grid_periodic)
+            raise api.ArgumentError(f"diffusion_terms: periodic axis {a} ({'xyz'[a]}) has extent {int(dims[a])} (a periodic axis needs at "
+                                    "least 3 points: at 2 the two neighbours coincide, at 1 the link is a self-link)")
     ext = [int(d) for d in dims] + [1] * (3 - ndim)
     nx, ny, nz = ext
     idx = np.arange(nx * ny * nz)
@@ -301,6 +319,9 @@ def diffusion_terms(shape, coeff, spacing=1.0, potential=None, boundary="dirichl
             has = pos[a] > 0 if sign < 0 else pos[a] < ext[a] - 1
             cs = c.copy()
             cs[has] = c[idx[has] + sign * stride[a]]
+            if per[a]:   # the wrap image: the other end of the line
+                cs[~has] = c[idx[~has] - sign * (ext[a] - 1) * stride[a]]
+                has = np.ones_like(has)
             e = (0.5 * taps[ndim + sign * (1 + a)]) * (c + cs)
             if boundary == "neumann":
                 e = np.where(has, e, 0.0)

@@ -314,12 +314,18 @@ end
 # ... with a VARIABLE, cell-centred coefficient (ks_operator_grid_var): A = -div(c(x) grad) + V(x) and its kin, the off-diagonal entry of
 # the link from row r to its neighbour s in direction k being fl(0.5 taps[k] * fl(c[r] + c[s])), formed in registers -- still nothing stored
 # per non-zero.  `coeff`: one real value per grid point (an `Array` of size `dims`, or a vector in row order), Float64 also for ComplexF64
-# operators; `dims`, `taps`, `potential` as for HipGridOperator (open boundaries, radius 1).  The products have the bits of the stored
-# matrix with the same entries.
+# operators; `dims`, `taps`, `potential` as for HipGridOperator (radius 1).  The products have the bits of the stored matrix with the
+# same entries.
+# `periodic`, `wrap`: as for HipGridOperator (ks_operator_grid_var_periodic) -- photonic crystals, a superlattice with a
+# position-dependent mass, diffusion on a torus.  A link that crosses the boundary of a periodic axis carries
+# fl(0.5 wrap[k] * fl(c[r] + c[s])) with s the wrap image at the other end of the line; t e^{+-i theta} = Bloch phases (Hermitian for
+# real c and symmetric real taps).
 function HipGridVariableOperator(ctx::HipContext, dims::NTuple{N,Integer}, taps::AbstractVector, coeff::AbstractArray{<:Real};
-                                 potential::Union{Nothing,AbstractArray} = nothing) where {N}
+                                 potential::Union{Nothing,AbstractArray} = nothing,
+                                 periodic::Union{Nothing,Bool,NTuple{N,Bool},AbstractVector{Bool}} = nothing,
+                                 wrap::Union{Nothing,AbstractVector} = nothing) where {N}
     1 <= N <= 3 || throw(ArgumentError("a grid has 1, 2 or 3 dimensions"))
-    T = (eltype(taps) <: Complex || (potential !== nothing && eltype(potential) <: Complex)) ? ComplexF64 : Float64
+    T = (eltype(taps) <: Complex || (potential !== nothing && eltype(potential) <: Complex) || (wrap !== nothing && eltype(wrap) <: Complex)) ? ComplexF64 : Float64
     length(taps) == 2N + 1 || throw(DimensionMismatch("a $(N)-D grid takes $(2N + 1) taps"))
     n = prod(Int64.(dims))
     length(coeff) == n || throw(DimensionMismatch("coeff must have $(n) entries"))
@@ -327,6 +333,19 @@ function HipGridVariableOperator(ctx::HipContext, dims::NTuple{N,Integer}, taps:
     d = Int64[dims...]; t = Vector{T}(taps); c = Vector{Float64}(vec(coeff))
     v = potential === nothing ? T[] : Vector{T}(vec(potential))
     r = Ref{Ptr{Cvoid}}(C_NULL)
+    if periodic !== nothing || wrap !== nothing
+        flags = periodic === nothing ? fill(Cint(0), N) : periodic isa Bool ? fill(Cint(periodic), N) : Cint[periodic...]
+        length(flags) == N || throw(DimensionMismatch("periodic takes one flag per axis ($(N))"))
+        (wrap === nothing || length(wrap) == 2N) || throw(DimensionMismatch("a $(N)-D grid takes $(2N) wrap values"))
+        w = wrap === nothing ? T[] : Vector{T}(wrap)
+        GC.@preserve d t c v flags w begin
+            check(ccall((:ks_operator_grid_var_periodic, LIB), Cint,
+                        (Ptr{Cvoid}, Cint, Ptr{Int64}, Cint, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cvoid}, Ptr{Cint}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),
+                        ctx.h, Cint(N), pointer(d), dtype_code(T), pointer(t), pointer(c), potential === nothing ? C_NULL : pointer(v),
+                        pointer(flags), wrap === nothing ? C_NULL : pointer(w), r))
+        end
+        return _finish_operator(T, r[], n, ctx, nothing)
+    end
     GC.@preserve d t c v begin
         check(ccall((:ks_operator_grid_var, LIB), Cint,
                     (Ptr{Cvoid}, Cint, Ptr{Int64}, Cint, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),

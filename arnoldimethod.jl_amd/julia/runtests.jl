@@ -173,4 +173,28 @@ hip_workspace(::Type{T}, n::Int, maxdim::Int) where {T} = ArnoldiWorkspace(HipBa
         @test history2.converged
         @test maximum(abs.(sort(real(decomp2.eigenvalues))[1:10] .- exact)) < 1e-6
     end
+
+    # ------------------------------------------------------------------------------------------ readme.md:24-49 on a ring, matrix-free
+    @testset "Variable-coefficient grid operator with a periodic axis and Bloch phases" begin
+        n, θ = 100, 0.7
+        c = [1.0 + 0.5 * sin(2π * k / n)^2 for k = 1:n]
+        taps = [-1.0, 0.0, -1.0]
+        wrap = [taps[1] * exp(-im * θ), taps[3] * exp(im * θ)]
+        e(r, s) = 0.5 * (c[r] + c[s])                       # minus the entry of the link r -> s (the taps are -1)
+        nb(r, k) = mod1(r + k, n)
+        diagonal = [e(r, nb(r, -1)) + e(r, nb(r, 1)) for r = 1:n]
+        A = spzeros(ComplexF64, n, n)
+        for r = 1:n
+            A[r, r] = diagonal[r]
+            A[r, nb(r, -1)] = -e(r, nb(r, -1)) * (r == 1 ? exp(-im * θ) : 1)
+            A[r, nb(r, 1)] = -e(r, nb(r, 1)) * (r == n ? exp(im * θ) : 1)
+        end
+        @test norm(A - A') == 0
+        Ad = HipGridVariableOperator(ctx, (n,), taps, c; potential = diagonal, periodic = true, wrap = wrap)
+        decomp, history = partialschur(Ad, nev = 4, tol = 1e-10, which = :SR)
+        @test history.converged
+        exact = sort(eigvals(Hermitian(Matrix(A))))[1:4]
+        @test maximum(abs.(imag(decomp.eigenvalues))) < 1e-10
+        @test maximum(abs.(sort(real(decomp.eigenvalues))[1:4] .- exact)) < 1e-8
+    end
 end

@@ -300,6 +300,31 @@ int ks_operator_grid_star(ks_ctx* ctx, int ndim, const int64_t* dims /* ndim ent
 int ks_operator_grid_var(ks_ctx* ctx, int ndim, const int64_t* dims /* ndim entries: nx[, ny[, nz]] */, int dtype,
                          const void* taps /* 2*ndim+1 values of dtype */, const double* coeff /* n values */,
                          const void* potential /* n values of dtype, or NULL */, ks_operator** out);
+/* (xi-b) ... with a variable coefficient AND periodic axes: photonic and phononic crystals (div (1 / eps) grad at a k-point), a
+ * superlattice with a position-dependent mass, heterogeneous diffusion on a torus -- mul!(y, A, x), src/expansion.jl:121, still with
+ * nothing stored per non-zero and the traffic of (xi).  Everything of (xi) and of (ix) holds, combined as follows.  DEFINITION -- the
+ * operator is the matrix ks_host_grid_var_matrix_periodic returns:
+ *   periodic    as in (ix): ndim flags in the order of dims, NULL: no axis wraps; a periodic axis needs extent >= 3
+ *   wrap        as in (ix): 2 ndim values of `dtype` in the order of the taps without the centre, NULL: the taps themselves; values
+ *               of periodic axes must be finite, values of open axes are neither read nor checked
+ *   half wrap   hw_k = 0.5 wrap_k, computed once on the host like the half taps (componentwise for ComplexF64)
+ *   entry       an interior link in slot k: fl(h_k * fl(c[r] + c[s])) as in (xi); a link that crosses the boundary in direction k,
+ *               s being the wrap image at the other end of the line:  A[r, s] = fl(hw_k * fl(c[r] + c[s]))  (ComplexF64: the two real
+ *               multiplications)
+ *   diagonal    centre + potential[r], as in (viii)
+ *   row         a sub-sequence of the 13 slots of (ix), in that order; nnz as in (ix)
+ *   product     every product A[r, s] x[s] rounded on its own and added to +0.0 in slot order: bit-identical to ks_operator_csr of
+ *               the matrix
+ * With no periodic axis the operator is that of ks_operator_grid_var (same matrix, same kernel).  With c == 1 the matrix is bit for bit
+ * that of ks_host_grid_matrix_periodic (0.5 w * 2 is exact).  With real c, taps with t_{-a} = conj(t_{+a}) and Bloch wrap values
+ * t_{+-a} e^{+-i theta_a} the matrix is exactly Hermitian: c[r] + c[s] commutes and the two parts are rounded separately.
+ * KS_ERR_ARGUMENT: the refusals of (xi), then those of (ix); the message names the cause and the axis or index.  ks_operator_size
+ * reports the periodic nnz; the bytes of a product are those of (xi).  Single-GPU contexts only; the Newton step of the s-step
+ * expansion is one launch of the same kernel, as in (viii). */
+int ks_operator_grid_var_periodic(ks_ctx* ctx, int ndim, const int64_t* dims /* ndim entries: nx[, ny[, nz]] */, int dtype,
+                                  const void* taps /* 2*ndim+1 values of dtype */, const double* coeff /* n values */,
+                                  const void* potential /* n values of dtype, or NULL */, const int* periodic /* ndim flags, or NULL */,
+                                  const void* wrap /* 2*ndim values of dtype, or NULL */, ks_operator** out);
 /* (xii) ... with the DIAGONAL neighbours: the 3-, 9- or 27-point BOX stencil, a link to every neighbour at distance one in the maximum
  * norm -- the mixed derivatives of -div(D grad) + V with a full constant tensor D (anisotropic media, effective-mass tensors, a lattice
  * in sheared coordinates), compact (Mehrstellen) Laplacians, stiffness and mass matrices of multilinear (Q1) finite elements on a uniform
@@ -726,6 +751,16 @@ int ks_host_grid_matrix_star(int ndim, const int64_t* dims, int radius, int dtyp
  * involved. */
 int ks_host_grid_var_matrix(int ndim, const int64_t* dims, int dtype, const void* taps, const double* coeff, const void* potential,
                             int64_t* rowptr /* n+1 */, int32_t* colidx, void* val, int64_t cap, int64_t* nnz);
+/* ... and the matrix that DEFINES ks_operator_grid_var_periodic (mul!(y, A, x), src/expansion.jl:121): `coeff`, `periodic` and `wrap` as
+ * there; an interior link carries fl(0.5 t_k * fl(c[r] + c[s])), a link that crosses the boundary of a periodic axis
+ * fl(0.5 wrap_k * fl(c[r] + c[s])) with s the wrap image; every row a sub-sequence of the 13 slots of (ix), *nnz as for
+ * ks_host_grid_matrix_periodic (also reported when cap is too small).  With no periodic axis the arrays are those of
+ * ks_host_grid_var_matrix, with c == 1 those of ks_host_grid_matrix_periodic.  Same refusals as that operator, except that no context is
+ * involved. */
+int ks_host_grid_var_matrix_periodic(int ndim, const int64_t* dims, int dtype, const void* taps, const double* coeff,
+                                     const void* potential, const int* periodic /* ndim flags, or NULL */,
+                                     const void* wrap /* 2*ndim values, or NULL */, int64_t* rowptr /* n+1 */, int32_t* colidx,
+                                     void* val, int64_t cap, int64_t* nnz);
 /* ... and the matrix that DEFINES ks_operator_grid_box (mul!(y, A, x), src/expansion.jl:121): `taps` holds 3^ndim values, every row is a
  * sub-sequence of the 27 slots (ascending columns), an entry is stored even where its tap is zero, *nnz = prod_a (3 m_a - 2) (also
  * reported when cap is too small).  In 1-D the arrays are those of ks_host_grid_matrix.  Same refusals as that operator, except that no

@@ -26,7 +26,10 @@ Float64, 7-point -Laplacian (+ a harmonic potential) on m x m x m grids.  Per si
                (b) csr_operator(host_grid_variable_matrix(...))    the same matrix stored: the only way to run it without (a)
                (c) grid_variable_operator without a diagonal       24 n bytes
                (d) grid_operator with a potential                  24 n bytes: (a) of the plain run, the constant-coefficient floor
-             and the solve on (a) and (b).
+             and the solve on (a) and (b).  With --periodic as well (ks_operator_grid_var_periodic), on the torus:
+               (e) grid_variable_operator(..., periodic=True) with the diagonal of the torus     32 n bytes, as (a)
+               (f) csr_operator(host_grid_variable_matrix(..., periodic=True))                   the same matrix stored
+             in the same rounds, and the solve on (e) and (f) too.
              --box (ks_operator_grid_box) runs the 27-point box stencil of -div(D grad) + V with a full constant tensor D
              (extras.tensor_laplacian_taps; 19 of the 27 taps are non-zero, all 27 are stored and multiplied) in the same rounds as
              the 7-point operator, the floor:
@@ -36,7 +39,7 @@ Float64, 7-point -Laplacian (+ a harmonic potential) on m x m x m grids.  Per si
                (d) grid_operator with a potential                  24 n bytes: (a) of the plain run, the 7-point floor
              and the solve on (a) and (b).
              --complex runs the grid operators of the run that the other switches select -- (a) and (c); --periodic: (e) alone;
-             --variable: (a), (c), (d) -- in the same rounds with ComplexF64 taps, potential and vectors (twice the bytes; c stays
+             --variable: (a), (c), (d); --variable --periodic: (e) alone, at the k-point theta = (0.7, 1.1, 1.9) (Bloch wrap values) -- in the same rounds with ComplexF64 taps, potential and vectors (twice the bytes; c stays
              Float64): products only, no stored matrix and no solve.  --wide puts them on the m^2 x 1 x m grid, which takes the
              one-row tiles.
              The HIP-event time is taken per round as well (`event_rounds`): its mean and max - min are what two builds are
@@ -289,8 +292,8 @@ def main_variable(args):
     constant-coefficient operator with a potential (d) as the floor, in the same rounds; the solve on (a) and (b)."""
     from arnoldimethod_jl_amd import extras
 
-    if args.periodic or args.radius is not None:
-        raise SystemExit("--variable takes no --periodic and no --radius")
+    if args.radius is not None:
+        raise SystemExit("--variable takes no --radius")
     ctx = ks.Context(0)
     for m in (int(s) for s in args.sizes.split(",")):
         shape, n = (m, m, m), m ** 3
@@ -306,11 +309,19 @@ def main_variable(args):
             "d_grid_potential": ks.grid_operator(shape, LAPLACE, V, ctx=ctx),
         }
         nnz = A.nnz
+        stored = {"b_stored_variable": nnz}
+        if args.periodic:
+            tp, dp = extras.diffusion_terms(shape, c, potential=V, periodic=True)
+            Ap = ks.host_grid_variable_matrix(shape, tp, c, dp, periodic=True)
+            ops["e_var_periodic"] = ks.grid_variable_operator(shape, tp, c, dp, ctx=ctx, periodic=True)
+            ops["f_stored_var_periodic"] = ks.csr_operator(Ap, ctx)
+            stored["f_stored_var_periodic"] = Ap.nnz
+            del Ap
         setup_s = time.perf_counter() - t0
         del A
-        fmt = {"b_stored_variable": ops["b_stored_variable"].format}
-        by = {"a_var_diagonal": 32.0 * n, "c_var_plain": 24.0 * n, "d_grid_potential": 24.0 * n,
-              "b_stored_variable": fmt["b_stored_variable"]["bytes_per_nnz"] * nnz + 16.0 * n}
+        fmt = {k: ops[k].format for k in stored}
+        by = {"a_var_diagonal": 32.0 * n, "c_var_plain": 24.0 * n, "d_grid_potential": 24.0 * n, "e_var_periodic": 32.0 * n}
+        by.update({k: fmt[k]["bytes_per_nnz"] * stored[k] + 16.0 * n for k in stored})
         out = dict(m=m, n=n, variable=True, nnz=nnz, setup_seconds=round(setup_s, 2), formats=fmt, chains=args.chains, products_per_round=args.chains * MAXDIM)
         prod = bench_products(ctx, ops, n, args.rounds, args.chains)
         for name, s in prod.items():
@@ -319,7 +330,8 @@ def main_variable(args):
             s["hbm_fraction_of_kernels"] = by[name] / (s["event_us"] * 1e-6) / PEAK
         out["us_per_product"] = prod
         if not args.no_solve:
-            runs = {name: Solve(ctx, ops[name], n) for name in ("a_var_diagonal", "b_stored_variable")}
+            names = ("a_var_diagonal", "b_stored_variable") + (("e_var_periodic", "f_stored_var_periodic") if args.periodic else ())
+            runs = {name: Solve(ctx, ops[name], n) for name in names}
             for s in runs.values():
                 s.cycles(3)
             rate = {name: [] for name in runs}
@@ -328,6 +340,8 @@ def main_variable(args):
                     rate[name].append(s.cycles(args.cycles))
             out["iterations_per_s"] = {name: stats(v) for name, v in rate.items()}
             out["same_restart_trail"] = runs["a_var_diagonal"].trail == runs["b_stored_variable"].trail
+            if args.periodic:
+                out["same_restart_trail_periodic"] = runs["e_var_periodic"].trail == runs["f_stored_var_periodic"].trail
             out["blocks"] = {name: s.ws.sstep_info["blocks"] for name, s in runs.items()}
             for s in runs.values():
                 s.ws.close()
@@ -395,15 +409,22 @@ def main_complex(args):
     from arnoldimethod_jl_amd import extras
 
     R = 1 if args.radius is None else args.radius
-    if R not in (1, 2, 3, 4) or (R > 1 and (args.periodic or args.variable)) or (args.periodic and args.variable):
-        raise SystemExit("--complex takes one of --periodic, --radius 2 / 3 / 4 and --variable")
+    if R not in (1, 2, 3, 4) or (R > 1 and (args.periodic or args.variable)):
+        raise SystemExit("--complex takes one of --periodic, --radius 2 / 3 / 4 and --variable (or --variable --periodic)")
     phase = 1.0 + 0.25j
     ctx = ks.Context(0)
     for m in (int(s) for s in args.sizes.split(",")):
         shape, n = ((m * m, 1, m) if args.wide else (m, m, m)), m ** 3
         V = phase * ks.matrices.harmonic_potential(shape)
         t0 = time.perf_counter()
-        if args.variable:
+        if args.variable and args.periodic:      # a Bloch operator, theta != 0: Hermitian, every wrap value complex
+            c = jump_coefficient(shape)
+            per = tuple(e >= 3 for e in shape)
+            taps, diag = extras.diffusion_terms(shape, c, potential=V.real, periodic=per)
+            ops = {"e_var_periodic": ks.grid_variable_operator(shape, taps, c, diag, ctx=ctx, periodic=per,
+                                                               wrap=extras.bloch_wrap(taps, (0.7, 1.1, 1.9)))}
+            by = {"e_var_periodic": 56.0 * n}
+        elif args.variable:
             c = jump_coefficient(shape)
             taps, diag = extras.diffusion_terms(shape, c, potential=V.real)
             ops = {
