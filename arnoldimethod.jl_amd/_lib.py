@@ -101,6 +101,7 @@ PROTOTYPES = {
     "ks_operator_grid_var": [vp, i32, vp, i32, vp, vp, vp, P(vp)],
     "ks_operator_grid_var_periodic": [vp, i32, vp, i32, vp, vp, vp, vp, vp, P(vp)],
     "ks_operator_grid_box": [vp, i32, vp, i32, vp, vp, P(vp)],
+    "ks_operator_grid_box_periodic": [vp, i32, vp, i32, vp, vp, vp, vp, P(vp)],
     "ks_operator_destroy": [vp],
     "ks_operator_size": [vp, P(i64), P(i64), P(C.c_int)],
     "ks_operator_format": [vp, P(C.c_double), P(C.c_int), P(C.c_int)],
@@ -175,6 +176,7 @@ PROTOTYPES = {
     "ks_host_grid_var_matrix": [i32, vp, i32, vp, vp, vp, vp, vp, vp, i64, P(i64)],
     "ks_host_grid_var_matrix_periodic": [i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, P(i64)],
     "ks_host_grid_box_matrix": [i32, vp, i32, vp, vp, vp, vp, vp, i64, P(i64)],
+    "ks_host_grid_box_matrix_periodic": [i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, P(i64)],
     "ks_host_tridiag_solve": [i64, i32, vp, vp, vp, dbl, dbl, i32, i32, vp, i64, vp, i64, P(C.c_int), P(dbl), P(dbl)],
     "ks_host_tridiag_info": [i64, i32, vp, vp, vp, dbl, dbl, i32, P(C.c_int), vp, P(i64), P(dbl), P(dbl)],
     "ks_last_words": [C.c_char_p, i32],

@@ -725,13 +725,51 @@ def host_grid_variable_matrix(shape, taps, coeff, potential=None, dtype=None, pe
                           None if v is None else v.ctypes.data, flags.ctypes.data, None if w is None else w.ctypes.data)
 
 
-def _grid_box_nnz(dims):
-    """(n, nnz) of a box-stencil grid matrix, nnz = prod_a (3 m_a - 2); (0, 0) for a shape that the library refuses."""
+def _grid_box_nnz(dims, flags=None):
+    """(n, nnz) of a box-stencil grid matrix, nnz = prod_a (periodic_a ? 3 m_a : 3 m_a - 2); (0, 0) for a shape that the library
+    refuses (so do extents below 3 on a periodic axis: the count is then never used)."""
     n, _ = _grid_nnz(dims)
-    return n, (math.prod(3 * int(d) - 2 for d in dims) if n else 0)
+    flags = [0] * len(dims) if flags is None else flags
+    return n, (math.prod(3 * int(d) - (0 if f else 2) for d, f in zip(dims, flags)) if n else 0)
 
 
-def grid_box_operator(shape, taps, potential=None, dtype=None, ctx: Context | None = None) -> Operator:
+def _grid_box_links_args(dims, t, v, dt, dtype, periodic, links):
+    """(dtype, taps, potential, flags, links or None) of a box-stencil grid operator with periodic axes: `periodic` as for
+    `_grid_wrap_args`, `links` 5^ndim values, flat or of shape (5,) * ndim in [e_z, e_y, e_x] order.  A complex `links` promotes the
+    element type like a complex `wrap` does; a pinned Float64 refuses an imaginary part."""
+    ndim = int(dims.size)
+    dt, t, v, flags, _ = _grid_wrap_args(dims, t, v, dt, dtype, periodic, None)
+    w = None
+    if links is not None:
+        w = np.asarray(links)
+        if w.shape == (5,) * ndim:
+            w = w.reshape(-1)
+        if w.shape != (5 ** ndim,):
+            raise DimensionMismatch(f"the box stencil of a {ndim}-D grid takes {5 ** ndim} link values by class, flat or of shape "
+                                    f"{(5,) * ndim} ([e_z, e_y, e_x]), got shape {w.shape}")
+        if w.dtype.kind == "c" and dt.kind == "f":
+            if dtype is None:   # promote, like complex taps do
+                dt = np.dtype(np.complex128)
+                t = t.astype(dt)
+                v = None if v is None else v.astype(dt)
+            else:
+                # (entries that are never read may hold anything: the classes that are read decide)
+                read = _grid_box_links_read(ndim, flags)
+                if np.any(w.imag[read] != 0):
+                    raise ArgumentError("links has an imaginary part but the element type is Float64 (KS_F64)")
+        w = np.ascontiguousarray(w.real if dt.kind == "f" else w, dtype=dt)
+    return dt, t, v, flags, w
+
+
+def _grid_box_links_read(ndim, flags) -> np.ndarray:
+    """Which of the 5^ndim link values the library reads (flat, bool): some axis has class 0 or 4, and every such axis is periodic."""
+    e = np.indices((5,) * ndim).reshape(ndim, -1)[::-1]   # e[a]: the class along axis a (x first) of every flat index
+    cross = (e == 0) | (e == 4)
+    per = np.asarray(flags, dtype=bool)[:, None]
+    return cross.any(axis=0) & ~(cross & ~per).any(axis=0)
+
+
+def grid_box_operator(shape, taps, potential=None, dtype=None, ctx: Context | None = None, periodic=None, links=None) -> Operator:
     """Matrix-free operator of a constant-coefficient 3-, 9- or 27-point BOX stencil plus a per-point diagonal term on a grid
     (`ks_operator_grid_box`): mul!(y, A, x), src/expansion.jl:121, for stencils that link a point to its diagonal neighbours too --
     the mixed derivatives of -div(D grad) + V with a full constant tensor D (`extras.tensor_laplacian_taps`), compact (Mehrstellen)
@@ -744,27 +782,51 @@ def grid_box_operator(shape, taps, potential=None, dtype=None, ctx: Context | No
     shape (3,) * ndim in C order ([dz, dy, dx], so that `taps.ravel()` is the slot order).  Row r has the entry taps[k] at column
     r + dx + nx (dy + ny dz) for every slot whose neighbour lies inside the grid (stored even where the tap is zero); the diagonal
     entry is centre + potential[r].  The operator is exactly the matrix `host_grid_box_matrix` returns, and its products have the
-    bits `csr_operator` of that matrix gives.  Periodic axes, a variable coefficient and a radius above 1 are not offered.
+    bits `csr_operator` of that matrix gives.  A variable coefficient and a radius above 1 are not offered.
 
-    `operator.grid_info`: shape, taps (flat), has_potential, box=True, bytes_per_row."""
+    `periodic` (`ks_operator_grid_box_periodic`): True, or one bool per axis in the order of `shape`, as for `grid_operator` (extent
+    >= 3 on such an axis) -- a crystal in a non-orthogonal cell, Q1 elements or a compact Laplacian on a torus.  A diagonal link can
+    cross two or three cell faces at once, so the entries of the crossing links are given per CLASS: `links` holds 5^ndim values,
+    flat or of shape (5,) * ndim in [e_z, e_y, e_x] order, the class e along an axis being 0 = offset -1 across the boundary,
+    1 = offset -1, 2 = offset 0, 3 = offset +1, 4 = offset +1 across the boundary.  Only entries with a class 0 or 4, all on periodic
+    axes, are read (the others may hold anything, NaN included); None = the tap of the link's slot (a plain torus),
+    `extras.box_bloch_links(taps, theta)` = Bloch phases, `-extras.box_bloch_links(taps, np.zeros(ndim)).real` = antiperiodic.  At the
+    first point of a periodic axis a row takes the offsets in the order (0, +1, -1), at the last in the order (+1, -1, 0): ascending
+    columns.  A complex `links` promotes the element type; the traffic per row is unchanged.
+
+    `operator.grid_info`: shape, taps (flat), has_potential, box=True, bytes_per_row, and with `periodic` or `links` given also
+    periodic, links (flat, or None)."""
     ctx = ctx or default_context()
     lib = _lib.load()
     dt, dims, t, v = _grid_args(shape, taps, potential, dtype, box=True)
     h = C.c_void_p()
-    check(lib.ks_operator_grid_box(ctx._h, int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data, None if v is None else v.ctypes.data,
-                                   C.byref(h)))
-    return _grid_operator(ctx, h, dims, dt, t, v, box=True)
+    if periodic is None and links is None:
+        check(lib.ks_operator_grid_box(ctx._h, int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data,
+                                       None if v is None else v.ctypes.data, C.byref(h)))
+        return _grid_operator(ctx, h, dims, dt, t, v, box=True)
+    dt, t, v, flags, w = _grid_box_links_args(dims, t, v, dt, dtype, periodic, links)
+    check(lib.ks_operator_grid_box_periodic(ctx._h, int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data,
+                                            None if v is None else v.ctypes.data, flags.ctypes.data, None if w is None else w.ctypes.data,
+                                            C.byref(h)))
+    return _grid_operator(ctx, h, dims, dt, t, v, box=True, periodic=tuple(bool(f) for f in flags), links=None if w is None else w.copy())
 
 
-def host_grid_box_matrix(shape, taps, potential=None, dtype=None):
+def host_grid_box_matrix(shape, taps, potential=None, dtype=None, periodic=None, links=None):
     """The matrix that defines `grid_box_operator(shape, taps, potential)` as a scipy.sparse.csr_matrix (`ks_host_grid_box_matrix`:
     the host path, no device): ascending columns, nnz = prod_a (3 m_a - 2), an entry stored even where its tap is zero, the diagonal
-    entry centre + potential[r].  In 1-D it is the matrix of `host_grid_matrix`."""
+    entry centre + potential[r].  In 1-D it is the matrix of `host_grid_matrix`.  `periodic`, `links`: as for `grid_box_operator`
+    (`ks_host_grid_box_matrix_periodic`), nnz = prod_a (periodic_a ? 3 m_a : 3 m_a - 2)."""
     lib = _lib.load()
     dt, dims, t, v = _grid_args(shape, taps, potential, dtype, box=True)
-    n, nnz = _grid_box_nnz(dims)
-    return _host_grid_csr(lib.ks_host_grid_box_matrix, n, nnz, dt, int(dims.size), dims.ctypes.data, _dtype_code(dt), t.ctypes.data,
-                          None if v is None else v.ctypes.data)
+    head = (int(dims.size), dims.ctypes.data)
+    if periodic is None and links is None:
+        n, nnz = _grid_box_nnz(dims)
+        return _host_grid_csr(lib.ks_host_grid_box_matrix, n, nnz, dt, *head, _dtype_code(dt), t.ctypes.data,
+                              None if v is None else v.ctypes.data)
+    dt, t, v, flags, w = _grid_box_links_args(dims, t, v, dt, dtype, periodic, links)
+    n, nnz = _grid_box_nnz(dims, flags)
+    return _host_grid_csr(lib.ks_host_grid_box_matrix_periodic, n, nnz, dt, *head, _dtype_code(dt), t.ctypes.data,
+                          None if v is None else v.ctypes.data, flags.ctypes.data, None if w is None else w.ctypes.data)
 
 
 def host_operator(fn, n: int, dtype=np.float64, ctx: Context | None = None) -> Operator:

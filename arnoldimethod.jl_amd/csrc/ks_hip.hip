@@ -455,6 +455,13 @@ int ks_operator_grid_box(ks_ctx* ctx, int ndim, const int64_t* dims, int dtype, 
   });
 }
 
+int ks_operator_grid_box_periodic(ks_ctx* ctx, int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential,
+                                  const int* periodic, const void* links, ks_operator** out) {
+  return grid_operator_entry(ctx, dtype, out, "ks_operator_grid_box_periodic", [&](auto d, const std::string& who) {
+    return make_grid_box_periodic<decltype(d)>(ctx, who, ndim, dims, taps, potential, periodic, links);
+  });
+}
+
 int ks_operator_tridiag_info(const ks_operator* op, int* levels, int64_t* level_rows, int64_t* shortened_blocks, double* max_growth,
                              double* residual) {
   return guarded([&] {
@@ -1669,6 +1676,14 @@ int ks_host_grid_box_matrix(int ndim, const int64_t* dims, int dtype, const void
                             int32_t* colidx, void* val, int64_t cap, int64_t* nnz) {
   return grid_host_entry(dtype, "ks_host_grid_box_matrix", [&](auto h, const std::string& who) {
     grid::host_box_matrix_entry<decltype(h)>(who, ndim, dims, taps, potential, rowptr, colidx, val, cap, nnz);
+  });
+}
+
+int ks_host_grid_box_matrix_periodic(int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential,
+                                     const int* periodic, const void* links, int64_t* rowptr, int32_t* colidx, void* val, int64_t cap,
+                                     int64_t* nnz) {
+  return grid_host_entry(dtype, "ks_host_grid_box_matrix_periodic", [&](auto h, const std::string& who) {
+    grid::host_box_matrix_periodic_entry<decltype(h)>(who, ndim, dims, taps, potential, periodic, links, rowptr, colidx, val, cap, nnz);
   });
 }
 

@@ -387,6 +387,43 @@ def tensor_laplacian_taps(D, spacing=1.0, scale=1.0) -> np.ndarray:
     return t.ravel()
 
 
+def box_bloch_links(taps, theta) -> np.ndarray:
+    """The `links` array of `api.grid_box_operator(..., periodic=..., links=...)` for Bloch boundary conditions (a band structure
+    at the k-point theta_a = k_a L_a): 5^ndim complex values, flat in [e_z, e_y, e_x] order,
+
+        links[e] = taps[slot(e)] * exp(i sum_a theta_a c_a),   c_a = -1 / 0 / +1 for the class e_a = 0 / 1, 2, 3 / 4,
+
+    slot(e) being the slot of the link's offsets (-1 for the classes 0 and 1, 0 for 2, +1 for 3 and 4): a link that leaves the cell
+    through two or three faces carries the product of their phases, in the sign convention of `bloch_wrap`.  `taps`: the 3^ndim taps,
+    flat or of shape (3,) * ndim; `theta`: one phase per axis in the order of the shape (x[, y[, z]]).  The phase of a face is
+    computed once, the one of the opposite face is its conjugate, and conjugation commutes with every rounding of a complex product:
+    links[mirror(e)] == conj(links[e]) holds exactly, mirror: e_a -> 4 - e_a, whenever taps[-k] == conj(taps[k]) -- the operator is
+    then exactly Hermitian.  In 1-D [links[0], links[4]] is `bloch_wrap(taps, theta)` bit for bit.  The entries without a class 0
+    or 4 are the taps themselves (the library does not read them).
+
+    An antiperiodic cell (the sign -1 on every link that crosses):  `links = -box_bloch_links(taps, np.zeros(ndim)).real`."""
+    t = np.asarray(taps)
+    ndim = {3: 1, 9: 2, 27: 3}.get(t.size)
+    if ndim is None or t.shape not in ((3 ** ndim,), (3,) * ndim):
+        raise api.DimensionMismatch(f"taps must hold 3, 9 or 27 values, flat or of shape (3,) * ndim, got shape {t.shape}")
+    t = t.reshape((3,) * ndim)
+    th = np.atleast_1d(np.asarray(theta, dtype=np.float64))
+    if th.shape != (ndim,):
+        raise api.DimensionMismatch(f"theta takes one phase per axis ({ndim}), got shape {th.shape}")
+    plus = [np.exp(1j * th[a]) for a in range(ndim)]   # the + face of axis a; its - face: the conjugate
+    out = np.empty((5,) * ndim, dtype=np.complex128)
+    for e in np.ndindex(*out.shape):   # e = (e_z, e_y, e_x): axis a is index ndim - 1 - a
+        phase = None
+        for a in range(ndim):
+            ea = e[ndim - 1 - a]
+            if ea in (0, 4):
+                f = plus[a] if ea == 4 else np.conj(plus[a])
+                phase = f if phase is None else phase * f
+        tap = t[tuple(0 if c < 2 else 2 if c > 2 else 1 for c in e)]
+        out[e] = tap if phase is None else tap * phase
+    return out.reshape(-1)
+
+
 def q1_fem_taps(ndim, spacing=1.0):
     """(stiffness_taps, mass_taps) of multilinear (Q1) finite elements on a uniform grid for `api.grid_box_operator`, each 3^ndim
     Float64 values in slot order: the tensor products of the 1-D element matrices K_a = [-1, 2, -1] / h_a and

@@ -359,10 +359,19 @@ end
 # `taps`: 3^N values, an `Array` of size (3, ..., 3) indexed [dx + 2, dy + 2, dz + 2] (column-major: `vec(taps)` is the slot order
 # 9 (dz + 1) + 3 (dy + 1) + (dx + 1), ascending columns) or that vector; `dims`, `potential` as for HipGridOperator (open boundaries).
 # The products have the bits of the stored matrix with the same entries.
+# `periodic`, `links` (ks_operator_grid_box_periodic): `periodic` as for HipGridOperator (extent >= 3 on such an axis) -- a crystal in a
+# non-orthogonal cell, Q1 elements or a compact Laplacian on a torus.  A diagonal link can cross two or three cell faces at once, so the
+# entries of the crossing links are given per CLASS: `links` holds 5^N values, an `Array` of size (5, ..., 5) indexed
+# [e_x + 1, e_y + 1, e_z + 1] (column-major: `vec(links)` has the flat index 25 e_z + 5 e_y + e_x) or that vector, the class e along an
+# axis being 0 = offset -1 across the boundary, 1 = offset -1, 2 = offset 0, 3 = offset +1, 4 = offset +1 across the boundary.  Only
+# entries with a class 0 or 4, all on periodic axes, are read; `nothing` = the tap of the link's slot (a plain torus);
+# taps[slot] * exp(i sum_a theta_a c_a), c_a = -1 / 0 / +1 for the class 0 / 1, 2, 3 / 4 = Bloch phases.
 function HipGridBoxOperator(ctx::HipContext, dims::NTuple{N,Integer}, taps::AbstractArray;
-                            potential::Union{Nothing,AbstractArray} = nothing) where {N}
+                            potential::Union{Nothing,AbstractArray} = nothing,
+                            periodic::Union{Nothing,Bool,NTuple{N,Bool},AbstractVector{Bool}} = nothing,
+                            links::Union{Nothing,AbstractArray} = nothing) where {N}
     1 <= N <= 3 || throw(ArgumentError("a grid has 1, 2 or 3 dimensions"))
-    T = (eltype(taps) <: Complex || (potential !== nothing && eltype(potential) <: Complex)) ? ComplexF64 : Float64
+    T = (eltype(taps) <: Complex || (potential !== nothing && eltype(potential) <: Complex) || (links !== nothing && eltype(links) <: Complex)) ? ComplexF64 : Float64
     (length(taps) == 3^N && (ndims(taps) == 1 || size(taps) == ntuple(_ -> 3, N))) ||
         throw(DimensionMismatch("the box stencil of a $(N)-D grid takes $(3^N) taps"))
     n = prod(Int64.(dims))
@@ -370,6 +379,20 @@ function HipGridBoxOperator(ctx::HipContext, dims::NTuple{N,Integer}, taps::Abst
     d = Int64[dims...]; t = Vector{T}(vec(taps))
     v = potential === nothing ? T[] : Vector{T}(vec(potential))
     r = Ref{Ptr{Cvoid}}(C_NULL)
+    if periodic !== nothing || links !== nothing
+        flags = periodic === nothing ? fill(Cint(0), N) : periodic isa Bool ? fill(Cint(periodic), N) : Cint[periodic...]
+        length(flags) == N || throw(DimensionMismatch("periodic takes one flag per axis ($(N))"))
+        (links === nothing || (length(links) == 5^N && (ndims(links) == 1 || size(links) == ntuple(_ -> 5, N)))) ||
+            throw(DimensionMismatch("the box stencil of a $(N)-D grid takes $(5^N) link values"))
+        w = links === nothing ? T[] : Vector{T}(vec(links))
+        GC.@preserve d t v flags w begin
+            check(ccall((:ks_operator_grid_box_periodic, LIB), Cint,
+                        (Ptr{Cvoid}, Cint, Ptr{Int64}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cint}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),
+                        ctx.h, Cint(N), pointer(d), dtype_code(T), pointer(t), potential === nothing ? C_NULL : pointer(v),
+                        pointer(flags), links === nothing ? C_NULL : pointer(w), r))
+        end
+        return _finish_operator(T, r[], n, ctx, nothing)
+    end
     GC.@preserve d t v begin
         check(ccall((:ks_operator_grid_box, LIB), Cint,
                     (Ptr{Cvoid}, Cint, Ptr{Int64}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),

@@ -341,10 +341,42 @@ int ks_operator_grid_var_periodic(ks_ctx* ctx, int ndim, const int64_t* dims /* 
  *               bit-identical to ks_operator_csr of the matrix.  In 1-D the matrix is that of ks_host_grid_matrix with the same taps
  * KS_ERR_ARGUMENT as in (viii) ("tap k is not finite" for every one of the 3^ndim).  ks_operator_size reports n and nnz,
  * ks_operator_format 0 / 0 / -1.  The Newton step of the s-step expansion is one launch of the same kernel, as in (viii).  Periodic
- * axes, a variable coefficient and a radius above 1 are not offered for this stencil. */
+ * axes: (xii-b).  A variable coefficient and a radius above 1 are not offered for this stencil. */
 int ks_operator_grid_box(ks_ctx* ctx, int ndim, const int64_t* dims /* ndim entries: nx[, ny[, nz]] */, int dtype,
                          const void* taps /* 3^ndim values of dtype */, const void* potential /* n values of dtype, or NULL */,
                          ks_operator** out);
+/* (xii-b) ... the box stencil with PERIODIC axes: a crystal in a non-orthogonal cell (-div(D grad) + V with the constant tensor D of the
+ * sheared lattice, on a torus with Bloch phases), Q1 finite elements and compact Laplacians on a periodic cell -- mul!(y, A, x),
+ * src/expansion.jl:121, still with nothing stored per non-zero and the traffic of (xii).  Everything of (xii) holds, with the following
+ * additions.  A diagonal link can cross two or three cell faces at once, so the entries of the crossing links are given per CLASS.
+ * DEFINITION -- the operator is the matrix ks_host_grid_box_matrix_periodic returns:
+ *   periodic    as in (ix): ndim flags in the order of dims, NULL: no axis wraps; a periodic axis needs extent >= 3 (the refusal and
+ *               the message of (ix))
+ *   links       5^ndim values of dtype.  Along an axis the class e of a link is 0 = offset -1 across the boundary, 1 = offset -1,
+ *               2 = offset 0, 3 = offset +1, 4 = offset +1 across the boundary; the flat index is 25 e_z + 5 e_y + e_x in 3-D,
+ *               5 e_y + e_x in 2-D, e_x in 1-D.  An entry is READ, and checked for finiteness, only if at least one axis has class 0
+ *               or 4 and every axis with class 0 or 4 is periodic; every other entry is neither read nor checked (the taps hold the
+ *               all-interior entries).  NULL: every crossing link carries the tap of its slot (a plain torus)
+ *   entry       the link from r to the neighbour (ix + dx, iy + dy, iz + dz), taken modulo the extent on periodic axes: taps[slot] if it
+ *               crosses no boundary, otherwise links[e] with e_a = 0 or 4 on the axes it crosses and d_a + 2 on the others; a link
+ *               that would leave the grid along a non-periodic axis is absent
+ *   diagonal    centre + potential[r], as in (viii)
+ *   row         along an axis of extent m the present offsets at index i come in the order (-1, 0, +1) in the interior; (0, +1) at
+ *               i = 0 and (-1, 0) at i = m - 1 of an open axis; (0, +1, -1) at i = 0 and (+1, -1, 0) at i = m - 1 of a periodic axis.
+ *               A row runs over dz in that order, inside that over dy, inside that over dx: ascending column order, the columns being
+ *               lexicographic in (jz, jy, jx);  nnz = prod_a (periodic_a ? 3 m_a : 3 m_a - 2)
+ *   product     every product A[r, s] x[s] rounded on its own and added to +0.0 in this row order: bit-identical to ks_operator_csr of
+ *               the matrix
+ * With no periodic axis the operator is that of ks_operator_grid_box (same matrix, same kernel).  In 1-D the matrix is that of
+ * ks_host_grid_matrix_periodic with wrap = [links[0], links[4]].  With taps[-k] = conj(taps[k]) and links[mirror(e)] = conj(links[e]),
+ * mirror: e_a -> 4 - e_a (Bloch phases), the matrix is Hermitian.
+ * KS_ERR_ARGUMENT: the refusals of (xii), then those of (ix) for the flags and extents, then "link value k is not finite" with k the flat
+ * index.  ks_operator_size reports the periodic nnz, ks_operator_format 0 / 0 / -1.  Single-GPU contexts only; the Newton step of the
+ * s-step expansion is one launch of the same kernel, as in (viii). */
+int ks_operator_grid_box_periodic(ks_ctx* ctx, int ndim, const int64_t* dims /* ndim entries: nx[, ny[, nz]] */, int dtype,
+                                  const void* taps /* 3^ndim values of dtype */, const void* potential /* n values of dtype, or NULL */,
+                                  const int* periodic /* ndim flags, or NULL */, const void* links /* 5^ndim values of dtype, or NULL */,
+                                  ks_operator** out);
 int ks_operator_destroy(ks_operator* op);
 int ks_operator_size(const ks_operator* op, int64_t* n_local, int64_t* nnz, int* dtype);
 /* Device layout chosen for a stored matrix at upload (mul!(y, A, x), src/expansion.jl:121; all layouts give bit-identical y):
@@ -767,6 +799,13 @@ int ks_host_grid_var_matrix_periodic(int ndim, const int64_t* dims, int dtype, c
  * context is involved. */
 int ks_host_grid_box_matrix(int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential,
                             int64_t* rowptr /* n+1 */, int32_t* colidx, void* val, int64_t cap, int64_t* nnz);
+/* ... and the matrix that DEFINES ks_operator_grid_box_periodic (mul!(y, A, x), src/expansion.jl:121): `periodic` and `links` as there,
+ * every row in the order of (xii-b), *nnz = prod_a (periodic_a ? 3 m_a : 3 m_a - 2) (also reported when cap is too small).  With no
+ * periodic axis the arrays are those of ks_host_grid_box_matrix, in 1-D those of ks_host_grid_matrix_periodic with
+ * wrap = [links[0], links[4]].  Same refusals as that operator, except that no context is involved. */
+int ks_host_grid_box_matrix_periodic(int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential,
+                                     const int* periodic /* ndim flags, or NULL */, const void* links /* 5^ndim values, or NULL */,
+                                     int64_t* rowptr /* n+1 */, int32_t* colidx, void* val, int64_t cap, int64_t* nnz);
 /* The plan, the factors and the HOST apply of ks_operator_tridiag_solve without a device (docs/src/index.md:234-259: the
  * factorize / ldiv! pair of the shift-invert recipe): x[:, k] = (T - sigma I)^-1 b[:, k] for nrhs columns (column k at b + k ldb,
  * x + k ldx; b and x distinct), walking exactly the arrays the device kernels read, in their order.  Same refusals as the operator. */

@@ -37,7 +37,10 @@ Float64, 7-point -Laplacian (+ a harmonic potential) on m x m x m grids.  Per si
                (b) csr_operator(host_grid_box_matrix(...))         the same matrix stored: the only way to run it without (a)
                (c) grid_box_operator without a potential           16 n bytes
                (d) grid_operator with a potential                  24 n bytes: (a) of the plain run, the 7-point floor
-             and the solve on (a) and (b).
+             and the solve on (a) and (b).  With --periodic as well (ks_operator_grid_box_periodic), on the torus:
+               (e) grid_box_operator(..., periodic=True) with the potential                      24 n bytes, as (a)
+               (f) csr_operator(host_grid_box_matrix(..., periodic=True))                        the same matrix stored
+             in the same rounds as the open box operator (a), and the solve on (e) and (f) too.
              --complex runs the grid operators of the run that the other switches select -- (a) and (c); --periodic: (e) alone;
              --variable: (a), (c), (d); --variable --periodic: (e) alone, at the k-point theta = (0.7, 1.1, 1.9) (Bloch wrap values) -- in the same rounds with ComplexF64 taps, potential and vectors (twice the bytes; c stays
              Float64): products only, no stored matrix and no solve.  --wide puts them on the m^2 x 1 x m grid, which takes the
@@ -355,11 +358,12 @@ TENSOR = np.array([[1.0, 0.3, 0.2], [0.3, 1.5, 0.25], [0.2, 0.25, 2.0]])
 
 def main_box(args):
     """--box: the 27-point box operator of -div(D grad) + V with (a) and without (c) the potential, its stored matrix (b), and the
-    7-point operator with a potential (d) as the floor, in the same rounds; the solve on (a) and (b)."""
+    7-point operator with a potential (d) as the floor, in the same rounds; the solve on (a) and (b).  --periodic adds the operator
+    on the torus (e) and its stored matrix (f) to the rounds and to the solves."""
     from arnoldimethod_jl_amd import extras
 
-    if args.periodic or args.radius is not None or args.variable or args.complex:
-        raise SystemExit("--box takes no --periodic, --radius, --variable or --complex")
+    if args.radius is not None or args.variable or args.complex:
+        raise SystemExit("--box takes no --radius, --variable or --complex")
     taps = extras.tensor_laplacian_taps(TENSOR)
     ctx = ks.Context(0)
     for m in (int(s) for s in args.sizes.split(",")):
@@ -374,11 +378,18 @@ def main_box(args):
             "d_grid_potential": ks.grid_operator(shape, LAPLACE, V, ctx=ctx),
         }
         nnz = A.nnz
+        stored = {"b_stored_box": nnz}
+        if args.periodic:
+            Ap = ks.host_grid_box_matrix(shape, taps, V, periodic=True)
+            ops["e_box_periodic"] = ks.grid_box_operator(shape, taps, V, ctx=ctx, periodic=True)
+            ops["f_stored_box_periodic"] = ks.csr_operator(Ap, ctx)
+            stored["f_stored_box_periodic"] = Ap.nnz
+            del Ap
         setup_s = time.perf_counter() - t0
         del A
-        fmt = {"b_stored_box": ops["b_stored_box"].format}
-        by = {"a_box_potential": 24.0 * n, "c_box_plain": 16.0 * n, "d_grid_potential": 24.0 * n,
-              "b_stored_box": fmt["b_stored_box"]["bytes_per_nnz"] * nnz + 16.0 * n}
+        fmt = {k: ops[k].format for k in stored}
+        by = {"a_box_potential": 24.0 * n, "c_box_plain": 16.0 * n, "d_grid_potential": 24.0 * n, "e_box_periodic": 24.0 * n}
+        by.update({k: fmt[k]["bytes_per_nnz"] * stored[k] + 16.0 * n for k in stored})
         out = dict(m=m, n=n, box=True, nnz=nnz, setup_seconds=round(setup_s, 2), formats=fmt, chains=args.chains, products_per_round=args.chains * MAXDIM)
         prod = bench_products(ctx, ops, n, args.rounds, args.chains)
         for name, s in prod.items():
@@ -387,7 +398,8 @@ def main_box(args):
             s["hbm_fraction_of_kernels"] = by[name] / (s["event_us"] * 1e-6) / PEAK
         out["us_per_product"] = prod
         if not args.no_solve:
-            runs = {name: Solve(ctx, ops[name], n) for name in ("a_box_potential", "b_stored_box")}
+            names = ("a_box_potential", "b_stored_box") + (("e_box_periodic", "f_stored_box_periodic") if args.periodic else ())
+            runs = {name: Solve(ctx, ops[name], n) for name in names}
             for s in runs.values():
                 s.cycles(3)
             rate = {name: [] for name in runs}
@@ -396,6 +408,8 @@ def main_box(args):
                     rate[name].append(s.cycles(args.cycles))
             out["iterations_per_s"] = {name: stats(v) for name, v in rate.items()}
             out["same_restart_trail"] = runs["a_box_potential"].trail == runs["b_stored_box"].trail
+            if args.periodic:
+                out["same_restart_trail_periodic"] = runs["e_box_periodic"].trail == runs["f_stored_box_periodic"].trail
             out["blocks"] = {name: s.ws.sstep_info["blocks"] for name, s in runs.items()}
             for s in runs.values():
                 s.ws.close()
