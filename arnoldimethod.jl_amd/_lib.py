@@ -98,6 +98,7 @@ PROTOTYPES = {
     "ks_operator_grid": [vp, i32, vp, i32, vp, vp, P(vp)],
     "ks_operator_grid_periodic": [vp, i32, vp, i32, vp, vp, vp, vp, P(vp)],
     "ks_operator_grid_star": [vp, i32, vp, i32, i32, vp, vp, P(vp)],
+    "ks_operator_grid_star_periodic": [vp, i32, vp, i32, i32, vp, vp, vp, vp, P(vp)],
     "ks_operator_grid_var": [vp, i32, vp, i32, vp, vp, vp, P(vp)],
     "ks_operator_grid_var_periodic": [vp, i32, vp, i32, vp, vp, vp, vp, vp, P(vp)],
     "ks_operator_grid_box": [vp, i32, vp, i32, vp, vp, P(vp)],
@@ -173,6 +174,7 @@ PROTOTYPES = {
     "ks_host_grid_matrix": [i32, vp, i32, vp, vp, vp, vp, vp, i64, P(i64)],
     "ks_host_grid_matrix_periodic": [i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, P(i64)],
     "ks_host_grid_matrix_star": [i32, vp, i32, i32, vp, vp, vp, vp, vp, i64, P(i64)],
+    "ks_host_grid_matrix_star_periodic": [i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, P(i64)],
     "ks_host_grid_var_matrix": [i32, vp, i32, vp, vp, vp, vp, vp, vp, i64, P(i64)],
     "ks_host_grid_var_matrix_periodic": [i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, P(i64)],
     "ks_host_grid_box_matrix": [i32, vp, i32, vp, vp, vp, vp, vp, i64, P(i64)],

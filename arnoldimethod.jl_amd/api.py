@@ -480,7 +480,8 @@ def _grid_radius(radius, periodic, wrap):
     if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= 4:
         raise ArgumentError(f"radius must be an integer in 1...4 (the distance of the farthest neighbour along an axis), got {radius!r}")
     if int(radius) > 1 and (periodic is not None or wrap is not None):
-        raise ArgumentError(f"periodic / wrap are supported for radius 1 only, got radius = {int(radius)}")
+        raise ArgumentError(f"periodic / wrap are supported for radius 1 only here, got radius = {int(radius)}: "
+                            "grid_star_operator / host_grid_star_matrix take periodic axes at every radius")
     return int(radius)
 
 
@@ -521,10 +522,10 @@ def _grid_args(shape, taps, potential, dtype, radius=1, box=False):
     return dt, np.ascontiguousarray(dims), t, v
 
 
-def _grid_wrap_args(dims, t, v, dt, dtype, periodic, wrap):
+def _grid_wrap_args(dims, t, v, dt, dtype, periodic, wrap, radius=1):
     """(dtype, taps, potential, flags, wrap or None) of a grid operator with periodic axes: `periodic` a bool or one bool per axis,
-    `wrap` 2 ndim values in the order of the taps without the centre.  A complex `wrap` promotes the element type like complex taps
-    do; a pinned Float64 refuses an imaginary part."""
+    `wrap` 2 ndim radius values in the order of the taps without the centre.  A complex `wrap` promotes the element type like
+    complex taps do; a pinned Float64 refuses an imaginary part."""
     ndim = int(dims.size)
     if periodic is None:
         periodic = False
@@ -541,8 +542,10 @@ def _grid_wrap_args(dims, t, v, dt, dtype, periodic, wrap):
     w = None
     if wrap is not None:
         w = np.asarray(wrap)
-        if w.shape != (2 * ndim,):
-            raise DimensionMismatch(f"a {ndim}-D grid takes {2 * ndim} wrap values in the order of the taps without the centre, got shape {w.shape}")
+        if w.shape != (2 * ndim * radius,):
+            of = "" if radius == 1 else f" of radius {radius}"
+            raise DimensionMismatch(f"a {ndim}-D grid{of} takes {2 * ndim * radius} wrap values in the order of the taps without the centre, "
+                                    f"got shape {w.shape}")
         if w.dtype.kind == "c" and dt.kind == "f":
             if dtype is None:   # promote, like complex taps do
                 dt = np.dtype(np.complex128)
@@ -564,14 +567,15 @@ def _grid_operator(ctx, h, dims, dt, t, v, extra_bytes=0, **info) -> Operator:
 
 
 def _grid_nnz(dims, radius=1, flags=()):
-    """(n, nnz) of a grid matrix: the diagonal, the links of distance 1...radius and the two wrap links per line of a periodic axis.
-    (0, 0) for a shape that the library refuses (so do extents below 3 on a periodic axis: the count is then never used)."""
+    """(n, nnz) of a grid matrix: the diagonal, the links of distance 1...radius and, per line of a periodic axis, the 2 d links of
+    distance d that cross the boundary.  (0, 0) for a shape that the library refuses (so do extents below 2 radius + 1 on a periodic
+    axis: the count is then never used)."""
     ext = [int(d) for d in dims]
     n = math.prod(ext)
     if not (all(1 <= e < 2 ** 31 for e in ext) and n < 2 ** 31 - 1):
         return 0, 0
     nnz = n + sum(2 * max(e - d, 0) * (n // e) for e in ext for d in range(1, radius + 1))
-    return n, nnz + sum(2 * (n // e) for e, f in zip(ext, flags) if f)
+    return n, nnz + sum(2 * min(d, e) * (n // e) for e, f in zip(ext, flags) if f for d in range(1, radius + 1))
 
 
 def _host_grid_csr(entry, n, nnz, dt, *args):
@@ -647,6 +651,47 @@ def host_grid_matrix(shape, taps, potential=None, dtype=None, periodic=None, wra
     n, nnz = _grid_nnz(dims, 1, flags)
     return _host_grid_csr(lib.ks_host_grid_matrix_periodic, n, nnz, dt, *head, _dtype_code(dt), t.ctypes.data,
                           None if v is None else v.ctypes.data, flags.ctypes.data, None if w is None else w.ctypes.data)
+
+
+def grid_star_operator(shape, taps, radius, potential=None, dtype=None, ctx: Context | None = None, periodic=None, wrap=None) -> Operator:
+    """Matrix-free operator of a star stencil of radius 1...4 plus a per-point diagonal term on a grid whose axes may be PERIODIC
+    (`ks_operator_grid_star_periodic`): mul!(y, A, x), src/expansion.jl:121, for central differences of order 2 R on a crystal cell or
+    a supercell -- a band structure at a k-point with an 8th-order Laplacian -- with nothing stored per non-zero: 24 bytes per row
+    and product in Float64 (16 without a potential) at every radius.
+
+    `shape`, `taps`, `radius`, `potential`, `dtype`: as for `grid_operator(..., radius=radius)`; the radius is never inferred from
+    the length of `taps`.  `periodic`: True, or one bool per axis in the order of `shape`; a periodic axis needs an extent of at
+    least 2 radius + 1, an axis that does not wrap is truncated.  `wrap`: 2 ndim radius values in the order of the taps without the
+    centre ([-R z ... -1 z, -R y ... -1 y, -R x ... -1 x, +1 x ... +R x, +1 y ... +R y, +1 z ... +R z] in 3-D), the entry of the link
+    of that direction and distance where it crosses the cell boundary; None = the taps (plain periodicity),
+    `extras.bloch_wrap(taps, theta, radius=radius)` = Bloch phases.  A complex `wrap` promotes the element type like complex taps do.
+
+    The operator is exactly the matrix `host_grid_star_matrix` returns, and its products have the bits `csr_operator` of that matrix
+    gives.  With no periodic axis it is `grid_operator(..., radius=radius)`, with `radius=1` `grid_operator(..., periodic=, wrap=)`.
+    `operator.grid_info`: shape, taps, has_potential, bytes_per_row, periodic, wrap, radius."""
+    radius = _grid_radius(radius, None, None)
+    ctx = ctx or default_context()
+    lib = _lib.load()
+    dt, dims, t, v = _grid_args(shape, taps, potential, dtype, radius)
+    dt, t, v, flags, w = _grid_wrap_args(dims, t, v, dt, dtype, periodic, wrap, radius)
+    h = C.c_void_p()
+    check(lib.ks_operator_grid_star_periodic(ctx._h, int(dims.size), dims.ctypes.data, radius, _dtype_code(dt), t.ctypes.data,
+                                             None if v is None else v.ctypes.data, flags.ctypes.data, None if w is None else w.ctypes.data,
+                                             C.byref(h)))
+    return _grid_operator(ctx, h, dims, dt, t, v, periodic=tuple(bool(f) for f in flags), wrap=None if w is None else w.copy(), radius=radius)
+
+
+def host_grid_star_matrix(shape, taps, radius, potential=None, dtype=None, periodic=None, wrap=None):
+    """The matrix that defines `grid_star_operator(shape, taps, radius, potential, periodic=, wrap=)` as a scipy.sparse.csr_matrix
+    (`ks_host_grid_matrix_star_periodic`: the host path, no device): ascending columns, on a fully periodic grid 6 radius + 1 entries
+    per row, the diagonal entry centre + potential[r] stored even where it is zero."""
+    radius = _grid_radius(radius, None, None)
+    lib = _lib.load()
+    dt, dims, t, v = _grid_args(shape, taps, potential, dtype, radius)
+    dt, t, v, flags, w = _grid_wrap_args(dims, t, v, dt, dtype, periodic, wrap, radius)
+    n, nnz = _grid_nnz(dims, radius, flags)
+    return _host_grid_csr(lib.ks_host_grid_matrix_star_periodic, n, nnz, dt, int(dims.size), dims.ctypes.data, radius, _dtype_code(dt),
+                          t.ctypes.data, None if v is None else v.ctypes.data, flags.ctypes.data, None if w is None else w.ctypes.data)
 
 
 def _grid_coeff(dims, coeff):

@@ -3,7 +3,7 @@
 // kernel arguments, the only per-row datum is the diagonal entry centre + potential[r] (formed once on the host at upload, by the
 // code that the host matrix runs).  This file: what every grid kernel shares, then the constant-coefficient operators (k_grid: 3-, 5-
 // or 7-point stencil with open or periodic boundaries, ks_operator_grid / ks_operator_grid_periodic; k_grid_star: star stencils of
-// radius 2, 3, 4, ks_operator_grid_star).  ks_grid_var.hpp: the variable-coefficient operator (k_grid_var; open or periodic boundaries).
+// radius 2, 3, 4, ks_operator_grid_star; k_grid_star_per: the same with periodic axes, ks_operator_grid_star_periodic).  ks_grid_var.hpp: the variable-coefficient operator (k_grid_var; open or periodic boundaries).
 // Part of the ONE translation unit of libkschur_hip.so: included by ks_hip.hip after ks_tridiag.hpp.
 //
 // An operator IS the matrix its ks_host_grid_* entry returns: the kernel rounds every product on its own and adds the products of a
@@ -45,6 +45,9 @@
 // but those at an edge of the grid -- adds them in straight-line code; only the other waves test tap by tap.
 // Tiles: Float64 32 x 32 and 1024 x 1 at every radius; ComplexF64 the same at R = 2, 32 x 16 and 512 x 1 (two points per thread)
 // at R = 3 and 4, where four points of ten planes would take the kernel to one wave per SIMD (DESIGN).
+//
+// k_grid_star_per (R = 2, 3, 4 with periodic axes): a sibling of k_grid_star with the same march and the same tiles; its additions
+// are described at the kernel.
 #pragma once
 
 namespace ksd {
@@ -70,8 +73,56 @@ template <class T> struct GridPerDev : GridDev<T> {
 template <class T, int R> struct GridStarDev : GridGeom {
   T tap[6 * R + 1] = {};  // -R z ... -1 z, -R y ... -1 y, -R x ... -1 x, centre, +1 x ... +R x, +1 y ... +R y, +1 z ... +R z
 };
+// ... with periodic axes: the entries of the links of every distance where they cross the cell boundary, in the slots of the taps
+// with the centre left out (grid_wslot), and the axes that wrap
+template <class T, int R> struct GridStarPerDev : GridStarDev<T, R> {
+  T wrap[6 * R] = {};     // -R z ... -1 z, -R y ... -1 y, -R x ... -1 x, +1 x ... +R x, +1 y ... +R y, +1 z ... +R z
+  int px = 0, py = 0, pz = 0;
+};
+// the place in `wrap` of the link whose tap stands in slot k of the 6 R + 1
+template <int R> constexpr int grid_wslot(int k) { return k < 3 * R ? k : k - 1; }
 static_assert(sizeof(GridDev<double>) == 24 + 7 * 8 && sizeof(GridDev<cd>) == 24 + 7 * 16 && sizeof(GridStarDev<cd, 2>) == 24 + 13 * 16,
               "kernel arguments: six ints, then the taps with nothing between");
+static_assert(sizeof(GridStarPerDev<cd, 4>) <= 24 + 25 * 16 + 24 * 16 + 16, "kernel arguments of the periodic star kernel: below 1 KB");
+// The wrap values of the kernel's FIRST argument g (a GridStarPerDev<T, R>) as ONE 8-byte word per lane of every wave -- 6 R words
+// in Float64, 12 R in ComplexF64, lane j holds word j -- read back by lane number (grid_wrap_at, a compile-time lane) where a link
+// wraps.  Named as g.wrap[k] the compiler loads all 6 R values ahead of the z-loop, next to the taps they do not fit the scalar
+// registers, and every wave -- also those that never wrap -- pays for moving them to vector lanes and back; loaded from the argument
+// segment inside the branches of the waves at a periodic edge, each group waits for scalar memory once per point and plane
+// (DESIGN).  This costs two vector registers and two v_readlane per use.  The word is loaded through the argument segment's
+// address: g.wrap[lane] would make the compiler copy the struct to scratch.
+using GridArgWord = const double __attribute__((address_space(4)));
+template <class T, int R> __device__ __forceinline__ double grid_wrap_lane(int lane) {
+  static_assert(sizeof(GridStarPerDev<T, R>) == sizeof(GridStarDev<T, R>) + 6 * R * sizeof(T) + 16 && sizeof(GridStarDev<T, R>) % 8 == 0,
+                "wrap follows the taps with nothing between");
+  constexpr int NW = 6 * R * (int)(sizeof(T) / 8);
+  static_assert(NW <= 64, "one word per lane");
+#if defined(__HIP_DEVICE_COMPILE__)
+  using Byte = const char __attribute__((address_space(4)));
+  GridArgWord* w = (GridArgWord*)((Byte*)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(GridStarDev<T, R>));
+  return lane < NW ? w[lane] : 0.0;
+#else
+  return 0.0;
+#endif
+}
+__device__ __forceinline__ double grid_lane_f64(double v, int lane) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
+}
+// s plus the product c v of a link that exists or not (k).  Float64: the product where the link exists, else -0.0, is added --
+// s + (-0.0) has the bits of s for every s (+-0, NaN and Inf included), so this IS skipping an absent link, in straight-line code
+// where the sums of a thread's points overlap (the product of an absent link is formed and dropped: it never reaches s).
+// ComplexF64: a branch -- the straight-line form takes k_grid_star_per<ComplexF64, 32, 16, 4> to 255 + 6 registers and one wave per
+// SIMD (DESIGN).
+__device__ __forceinline__ double grid_add_if(double s, bool k, double c, double v) {
+  const double p = mul_nc(c, v);   // (formed ahead of the choice: inside it the compiler branches)
+  return add_(s, k ? p : -0.0);
+}
+__device__ __forceinline__ cd grid_add_if(cd s, bool k, cd c, cd v) { return k ? add_(s, mul_nc(c, v)) : s; }
+// wrap value k of the words in wl
+template <class T> __device__ __forceinline__ T grid_wrap_at(double wl, int k) {
+  if constexpr (sizeof(T) == 8) return grid_lane_f64(wl, k);
+  else return T{grid_lane_f64(wl, 2 * k), grid_lane_f64(wl, 2 * k + 1)};
+}
 
 // The in-plane tiles: TX x TY for ny > 1, WX x 1 for ny == 1.  Four points per thread; two (HALF) where four would cost the second
 // wave per SIMD: ComplexF64 with the planes of R >= 3 or with a coefficient beside x in registers and LDS (DESIGN).
@@ -81,6 +132,8 @@ template <bool HALF> struct GridTile {
 };
 constexpr bool grid_half(size_t elem, int R, bool var) { return elem == 16 && (R >= 3 || var); }
 template <class T, int R = 1, bool VAR = false> using GridTileOf = GridTile<grid_half(sizeof(T), R, VAR)>;
+// k_grid_star_per has a tile choice of its own (its registers are not those of k_grid_star)
+constexpr bool grid_star_per_half(size_t elem, int R) { return grid_half(elem, R, false); }
 
 // the LDS tile of a TX x TY tile with its halo of depth R
 template <int TX, int TY, int R> struct GridLds {
@@ -474,6 +527,220 @@ __global__ void __launch_bounds__(kBlock)
   for (int z = za; z < zb; z += 2) grid_star_steps<0, 2>(z, zb, step);
 }
 
+// ------------------------------------------------------------------------------------- radius 2, 3, 4 with periodic axes
+// k_grid_star_per: the march of k_grid_star (2 R + 2 register sets rotated by moves, two LDS tiles, one barrier per plane) on a
+// grid some of whose axes wrap (g.px, g.py, g.pz; extent >= 2 R + 1 each, so one wrap suffices everywhere).  A row is summed in
+// the order of include/kschur.h (x-b): per axis the +d links that wrap stand BEFORE the interior -d links, the -d links that wrap
+// AFTER the interior +d links, each with the wrap value of its direction and distance.
+// x and y: every LDS cell, owned or halo, whose coordinate c lies in [m, m + R) on a periodic axis is loaded from c - m, one in
+// [-R, 0) from c + m (the periodic k_grid's ldk / loff, R deep).  Beyond a partial last tile up to R slots of OWNED points hold
+// such images: they are loaded, written to the tile and never stored (`off` is the offset they LOAD from; it is the point's own
+// wherever in[] holds, and only there it serves the diagonal and the store).  A cell beyond the grid on both axes is read by no row.
+// Masks: bits 0 ... 15 as in k_grid_star (the interior tap exists), bits 16 ... 31 in the same layout: the tap wraps -- at R = 4
+// one full register per point.  A wave all of whose lanes have the R interior taps of a direction has no lane that wraps in it:
+// it skips the wrapped group with one uniform test and adds the interior group in straight-line code; only the other waves take
+// every slot link by link (grid_add_if).  The wrap values travel in the kernel arguments and stand in the lanes of one vector
+// register pair, read by compile-time lane number (grid_wrap_lane).
+// z: the plane index wraps in the plane load (uniform); the planes within R of either end of a periodic z add the wrapped z groups,
+// under a uniform test, from the register sets that hold those planes already.
+template <class T, int TX, int TY, int R>
+__global__ void __launch_bounds__(kBlock)
+    k_grid_star_per(const GridStarPerDev<T, R> g, const T* __restrict__ x, const T* __restrict__ diag, T* __restrict__ y,
+                    const DevState* __restrict__ st, int shifted, T theta, double sigma) {
+  if (st && st->breakdown >= 0) return;
+  using L = GridLds<TX, TY, R>;
+  constexpr int PPT = L::PPT, HY = L::HY, LW = L::LW, NH = L::NH;
+  constexpr int N = 2 * R + 2;                           // register sets: planes z - R ... z + R and the one in flight
+  constexpr unsigned FULL = (1u << R) - 1u;
+  static_assert(R >= 2, "radius 1 is k_grid");
+  __shared__ T tile[2][L::LH * LW];
+  const GridItem it = grid_item<TX, TY>(g);
+  const int za = it.za, zb = it.zb;
+  const int64_t P = it.P;
+  const int tid = (int)threadIdx.x;
+  const GridStore<T> store{y, P, shifted, theta, sigma};
+  const double wl = grid_wrap_lane<T, R>(tid & 63);   // the wrap values, a word per lane
+  // coordinate c of an LDS cell along an axis of extent m: where it is loaded from (outside [0, m): not at all)
+  auto img = [](int c, int m, int per) { return !per ? c : c < 0 ? c + m : c >= m && c < m + R ? c - m : c; };
+
+  int64_t off[PPT];   // in-plane offset the owned points are loaded from: their own, or that of the point they are the image of
+  int li[PPT];        // ... and their place in the LDS tile
+  bool in[PPT];       // inside the grid (a row of its own: diagonal, store)
+  bool ldk[PPT];      // loaded: inside the grid, or an image
+  unsigned msk[PPT];  // bit d - 1 / 4 + d - 1 / 8 + d - 1 / 12 + d - 1: has an interior neighbour at -d x / +d x / -d y / +d y;
+                      // 16 more: that link wraps
+#pragma unroll
+  for (int k = 0; k < PPT; ++k) {
+    int gx, gy;
+    grid_owned<TX, TY, R>(g, it, tid + k * kBlock, gx, gy, in[k], off[k], li[k]);
+    msk[k] = 0u;
+#pragma unroll
+    for (int d = 1; d <= R; ++d) {
+      if (in[k] && gx >= d) msk[k] |= 1u << (d - 1);
+      else if (in[k] && g.px) msk[k] |= 1u << (16 + d - 1);
+      if (in[k] && gx + d < g.nx) msk[k] |= 1u << (4 + d - 1);
+      else if (in[k] && g.px) msk[k] |= 1u << (20 + d - 1);
+      if (in[k] && gy >= d) msk[k] |= 1u << (8 + d - 1);
+      else if (in[k] && g.py) msk[k] |= 1u << (24 + d - 1);
+      if (in[k] && gy + d < g.ny) msk[k] |= 1u << (12 + d - 1);
+      else if (in[k] && g.py) msk[k] |= 1u << (28 + d - 1);
+    }
+    // (a point outside the grid has no row: with every interior bit set and no wrap bit it keeps no wave from the straight-line sums)
+    if (!in[k]) msk[k] = 0xffffu;
+    const int sx = img(gx, g.nx, g.px), sy = img(gy, g.ny, g.py);
+    ldk[k] = sx < g.nx && sy < g.ny;
+    off[k] = (int64_t)sy * g.nx + sx;
+  }
+  // this thread's halo cells: the R columns to the left, the R to the right, the R rows below, the R above
+  bool hin[NH];
+  int64_t hoff[NH];
+  int hli[NH];
+#pragma unroll
+  for (int j = 0; j < NH; ++j) {
+    const int c = tid + j * kBlock;
+    hin[j] = false;
+    hoff[j] = 0;
+    hli[j] = 0;
+    if (c < L::NHALO) {
+      int hx, hy;
+      if (c < R * TY) { hx = -1 - c / TY; hy = c % TY; }
+      else if (c < 2 * R * TY) { hx = TX + (c - R * TY) / TY; hy = (c - R * TY) % TY; }
+      else if (c < 2 * R * TY + R * TX) { hx = (c - 2 * R * TY) % TX; hy = -1 - (c - 2 * R * TY) / TX; }
+      else { hx = (c - 2 * R * TY - R * TX) % TX; hy = TY + (c - 2 * R * TY - R * TX) / TX; }
+      const int gx = img(it.x0 + hx, g.nx, g.px), gy = img(it.y0 + hy, g.ny, g.py);
+      hin[j] = gx >= 0 && gx < g.nx && gy >= 0 && gy < g.ny;
+      hoff[j] = (int64_t)gy * g.nx + gx;
+      hli[j] = (hy + HY) * LW + hx + R;
+    }
+  }
+  // plane z of a periodic z: planes -R ... -1 are the last R, planes nz ... nz + R - 1 the first (no load reaches further)
+  auto ldx = [&](int z, int64_t o, bool ok) {
+    if (g.pz) z = z < 0 ? z + g.nz : z >= g.nz ? z - g.nz : z;
+    return ok && z >= 0 && z < g.nz ? x[(int64_t)z * P + o] : zero_of(T{});
+  };
+
+  // Register sets, halo and diagonal registers: as in k_grid_star (with a periodic z set R + d holds plane z + d modulo nz).
+  T xr[N][PPT], dr[2][PPT], hr[2][NH];
+#pragma unroll
+  for (int j = 0; j < NH; ++j) {
+    hr[0][j] = ldx(za, hoff[j], hin[j]);
+    hr[1][j] = ldx(za + 1, hoff[j], hin[j] && za + 1 < zb);
+  }
+#pragma unroll
+  for (int k = 0; k < PPT; ++k) {
+#pragma unroll
+    for (int s = 0; s <= 2 * R; ++s) xr[s][k] = ldx(za - R + s, off[k], ldk[k]);
+    xr[N - 1][k] = zero_of(T{});
+    dr[0][k] = diag ? grid_ldd(diag, g, P, za, off[k], in[k]) : g.tap[3 * R];
+    dr[1][k] = dr[0][k];
+  }
+  // the R interior taps of one direction, as in k_grid_star
+  auto grp = [&](T s, unsigned gm, auto basec, auto sgnc, const T(&v)[R]) {
+    constexpr int BASE = decltype(basec)::value, SGN = decltype(sgnc)::value;
+    if (__all((gm & FULL) == FULL)) {
+#pragma unroll
+      for (int i = 0; i < R; ++i) {
+        const int d = SGN < 0 ? R - i : i + 1;
+        s = add_(s, mul_nc(g.tap[BASE + SGN * d], v[d - 1]));
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < R; ++i) {
+        const int d = SGN < 0 ? R - i : i + 1;
+        s = grid_add_if(s, gm >> (d - 1) & 1u, g.tap[BASE + SGN * d], v[d - 1]);
+      }
+    }
+    return s;
+  };
+  // ... and its links that wrap (bit d - 1 of wm), in the same order of d, with the wrap values: tap by tap
+  auto grw = [&](T s, unsigned wm, auto basec, auto sgnc, const T(&v)[R]) {
+    constexpr int BASE = decltype(basec)::value, SGN = decltype(sgnc)::value;
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const int d = SGN < 0 ? R - i : i + 1;
+      s = grid_add_if(s, wm >> (d - 1) & 1u, grid_wrap_at<T>(wl, grid_wslot<R>(BASE + SGN * d)), v[d - 1]);
+    }
+    return s;
+  };
+  // true in the waves that may hold a lane whose links of this direction wrap: those without all R interior taps, on a periodic axis
+  auto edge = [&](int per, unsigned gm) { return per && !__all((gm & FULL) == FULL); };
+  auto step = [&](int z, auto jc) {
+    constexpr int B = decltype(jc)::value & 1;
+    T* __restrict__ tl = tile[B];
+    const T(&xc)[PPT] = xr[R];
+    T(&xn)[PPT] = xr[N - 1];
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) tl[li[k]] = xc[k];
+#pragma unroll
+    for (int j = 0; j < NH; ++j) {
+      if (tid + j * kBlock < L::NHALO) tl[hli[j]] = hr[B][j];
+      hr[B][j] = ldx(z + 2, hoff[j], hin[j] && z + 2 < zb);
+    }
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+      xn[k] = ldx(z + R + 1, off[k], ldk[k] && z + 1 < zb);   // (the +R z tap of the next plane; beyond zb for the range's last R)
+      if (diag) dr[1 - B][k] = grid_ldd(diag, g, P, z + 1, off[k], in[k] && z + 1 < zb);
+    }
+    __syncthreads();
+    // the z taps as masks of the same kind (uniform): -d z is interior for d <= z, +d z for d <= nz - 1 - z; the others wrap
+    const unsigned zmm = (1u << min(R, z)) - 1u, zmp = (1u << min(R, g.nz - 1 - z)) - 1u;
+    const unsigned wzm = g.pz ? FULL & ~zmm : 0u, wzp = g.pz ? FULL & ~zmp : 0u;
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+      T s = zero_of(T{});
+      unsigned m = msk[k];
+      asm volatile("" : "+v"(m));   // (as in k_grid_star: the 8 R tests per point stay on this one register)
+      T vxm[R], vxp[R], vym[R], vyp[R];
+#pragma unroll
+      for (int d = 1; d <= R; ++d) {
+        vxm[d - 1] = tl[li[k] - d];
+        vxp[d - 1] = tl[li[k] + d];
+        if constexpr (HY > 0) {
+          vym[d - 1] = tl[li[k] - d * LW];
+          vyp[d - 1] = tl[li[k] + d * LW];
+        }
+      }
+      T vzm[R], vzp[R];
+#pragma unroll
+      for (int d = 1; d <= R; ++d) {
+        vzm[d - 1] = xr[R - d][k];
+        vzp[d - 1] = xr[R + d][k];
+      }
+      using M = std::integral_constant<int, -1>;
+      using Q = std::integral_constant<int, 1>;
+      using BZ = std::integral_constant<int, R>;
+      using BY = std::integral_constant<int, 2 * R>;
+      using BX = std::integral_constant<int, 3 * R>;
+      using CY = std::integral_constant<int, 4 * R>;
+      using CZ = std::integral_constant<int, 5 * R>;
+      if (wzp) s = grw(s, wzp, CZ{}, Q{}, vzp);
+      s = grp(s, zmm, BZ{}, M{}, vzm);
+      if constexpr (HY > 0) {
+        if (edge(g.py, m >> 12)) s = grw(s, m >> 28, CY{}, Q{}, vyp);
+        s = grp(s, m >> 8, BY{}, M{}, vym);
+      }
+      if (edge(g.px, m >> 4)) s = grw(s, m >> 20, BX{}, Q{}, vxp);
+      s = grp(s, m, BX{}, M{}, vxm);
+      s = add_(s, mul_nc(dr[B][k], xc[k]));
+      s = grp(s, m >> 4, BX{}, Q{}, vxp);
+      if (edge(g.px, m)) s = grw(s, m >> 16, BX{}, M{}, vxm);
+      if constexpr (HY > 0) {
+        s = grp(s, m >> 12, CY{}, Q{}, vyp);
+        if (edge(g.py, m >> 8)) s = grw(s, m >> 24, BY{}, M{}, vym);
+      }
+      s = grp(s, zmp, CZ{}, Q{}, vzp);
+      if (wzm) s = grw(s, wzm, BZ{}, M{}, vzm);
+      store(z, off[k], in[k], s, xc[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+#pragma unroll
+      for (int q = 0; q + 1 < N; ++q) xr[q][k] = xr[q + 1][k];
+    }
+  };
+  for (int z = za; z < zb; z += 2) grid_star_steps<0, 2>(z, zb, step);
+}
+
 }  // namespace ksd
 
 namespace {
@@ -558,6 +825,47 @@ Wrap<H> check_wrap(const std::string& who, Shape& s, int ndim, const void* taps_
   return W;
 }
 
+// ... of a star stencil of radius R (ks_host_grid_matrix_star_periodic, include/kschur.h (x-b)): wrap = 2 ndim R values in the order of
+// the taps without the centre, null = the taps themselves; a periodic axis needs 2 R + 1 points.  s.nnz: the 2 d links of distance d
+// per line that truncation leaves out are added.
+template <class H> struct WrapStar {
+  bool per[3] = {false, false, false};   // x, y, z
+  H w[24] = {};                          // the 6 R slots -R z ... -1 z, -R y ... -1 y, -R x ... -1 x, +1 x ... +R x, +1 y ..., +1 z ...
+                                         // (an axis that does not wrap, a missing dimension: zero, never used)
+  bool any() const { return per[0] || per[1] || per[2]; }
+};
+template <class H>
+WrapStar<H> check_wrap_star(const std::string& who, Shape& s, int ndim, int R, const void* taps_v, const int* periodic, const void* wrap_v) {
+  WrapStar<H> W;
+  if (!periodic) return W;
+  static const char* const axis[3] = {"x", "y", "z"};
+  const int64_t ext[3] = {s.nx, s.ny, s.nz};
+  const H* t = static_cast<const H*>(taps_v);
+  const H* w = static_cast<const H*>(wrap_v);
+  const int c = ndim * R;   // the centre among the taps; wrap has it left out
+  for (int a = 0; a < ndim; ++a) {
+    if (!periodic[a]) continue;
+    KS_REQUIRE(ext[a] >= 2 * R + 1, KS_ERR_ARGUMENT,
+               who + ": periodic axis " + std::to_string(a) + " (" + axis[a] + ") has extent " + std::to_string(ext[a]) + " at radius " +
+                   std::to_string(R) + " (a periodic axis needs at least 2 radius + 1 = " + std::to_string(2 * R + 1) +
+                   " points: below that two links of a row coincide or a link is a self-link)");
+    W.per[a] = true;
+    for (int d = 1; d <= R; ++d) {
+      // axis a, distance d: its - link is entry c - a R - d of wrap (and of the taps), its + link entry c + a R + d - 1 (tap c + a R + d)
+      const int km = c - a * R - d, kp = c + a * R + d - 1;
+      const H vm = w ? w[km] : t[km], vp = w ? w[kp] : t[kp + 1];
+      KS_REQUIRE(finite_(vm), KS_ERR_ARGUMENT,
+                 who + ": wrap value " + std::to_string(km) + " (-" + std::to_string(d) + " " + axis[a] + ") is not finite");
+      KS_REQUIRE(finite_(vp), KS_ERR_ARGUMENT,
+                 who + ": wrap value " + std::to_string(kp) + " (+" + std::to_string(d) + " " + axis[a] + ") is not finite");
+      W.w[(3 - a) * R - d] = vm;
+      W.w[(3 + a) * R + d - 1] = vp;
+      s.nnz += 2 * d * (s.n / ext[a]);
+    }
+  }
+  return W;
+}
+
 // the 2 ndim + 1 taps in the seven slots -z, -y, -x, centre, +x, +y, +z (slots of a missing dimension: zero, never used)
 template <class H> void seven_taps(int ndim, const H* t, H (&out)[7]) {
   for (H& o : out) o = H(0);
@@ -621,11 +929,13 @@ void host_matrix(const std::string& who, const Shape& s, int ndim, const H* taps
                   [&](int k, int64_t, int64_t, bool wrapped) { return wrapped ? W.w[k - (k > 3)] : t[k]; });
 }
 
-// The matrix that defines the star operator of radius R (ks_host_grid_matrix_star, include/kschur.h (x)): open boundaries, a row is
-// a sub-sequence of the 6 R + 1 slots.
+// The matrix that defines the star operator of radius R (ks_host_grid_matrix_star, ks_host_grid_matrix_star_periodic,
+// include/kschur.h (x), (x-b)): a row is a sub-sequence of the 6 R + 1 slots and, on a periodic axis (W.per), of the wrapped links
+// around them -- before the centre the +d links of an axis that wrap (the lowest columns of the axis) precede its -d links, after
+// it the -d links that wrap (the highest) follow its +d links.
 template <class H>
-void host_matrix_star(const std::string& who, const Shape& s, int ndim, int R, const H* taps, const H* pot, int64_t* rowptr,
-                      int32_t* colidx, H* val, int64_t cap, int64_t* nnz) {
+void host_matrix_star(const std::string& who, const Shape& s, int ndim, int R, const H* taps, const H* pot, const WrapStar<H>& W,
+                      int64_t* rowptr, int32_t* colidx, H* val, int64_t cap, int64_t* nnz) {
   csr_begin(who, s, rowptr, colidx, val, cap, nnz);
   H t[25];
   star_taps(ndim, R, taps, t);
@@ -636,13 +946,19 @@ void host_matrix_star(const std::string& who, const Shape& s, int ndim, int R, c
       for (int64_t ix = 0; ix < s.nx; ++ix, ++r) {
         rowptr[r] = q;
         auto put = [&](int64_t c, const H& v) { colidx[q] = (int32_t)c; val[q] = v; ++q; };
+        if (W.per[2]) for (int d = 1; d <= R; ++d) if (iz + d >= s.nz) put(r + (d - s.nz) * P, W.w[5 * R + d - 1]);
         for (int d = R; d >= 1; --d) if (iz >= d) put(r - d * P, t[R - d]);
+        if (W.per[1]) for (int d = 1; d <= R; ++d) if (iy + d >= s.ny) put(r + (d - s.ny) * s.nx, W.w[4 * R + d - 1]);
         for (int d = R; d >= 1; --d) if (iy >= d) put(r - d * s.nx, t[2 * R - d]);
+        if (W.per[0]) for (int d = 1; d <= R; ++d) if (ix + d >= s.nx) put(r + (d - s.nx), W.w[3 * R + d - 1]);
         for (int d = R; d >= 1; --d) if (ix >= d) put(r - d, t[3 * R - d]);
         put(r, pot ? diag_add(t[3 * R], pot[r]) : t[3 * R]);
         for (int d = 1; d <= R; ++d) if (ix + d < s.nx) put(r + d, t[3 * R + d]);
+        if (W.per[0]) for (int d = R; d >= 1; --d) if (ix < d) put(r + (s.nx - d), W.w[3 * R - d]);
         for (int d = 1; d <= R; ++d) if (iy + d < s.ny) put(r + d * s.nx, t[4 * R + d]);
+        if (W.per[1]) for (int d = R; d >= 1; --d) if (iy < d) put(r + (s.ny - d) * s.nx, W.w[2 * R - d]);
         for (int d = 1; d <= R; ++d) if (iz + d < s.nz) put(r + d * P, t[5 * R + d]);
+        if (W.per[2]) for (int d = R; d >= 1; --d) if (iz < d) put(r + (s.nz - d) * P, W.w[R - d]);
       }
   rowptr[s.n] = q;
 }
@@ -664,17 +980,36 @@ void host_matrix_star_entry(const std::string& who, int ndim, const int64_t* dim
   if (radius == 1)
     host_matrix<H>(who, s, ndim, static_cast<const H*>(taps), static_cast<const H*>(pot), Wrap<H>{}, rowptr, colidx, static_cast<H*>(val), cap, nnz);
   else
-    host_matrix_star<H>(who, s, ndim, radius, static_cast<const H*>(taps), static_cast<const H*>(pot), rowptr, colidx, static_cast<H*>(val), cap, nnz);
+    host_matrix_star<H>(who, s, ndim, radius, static_cast<const H*>(taps), static_cast<const H*>(pot), WrapStar<H>{}, rowptr, colidx,
+                        static_cast<H*>(val), cap, nnz);
+}
+
+// ... and the periodic star entry point (radius 1: the arrays of ks_host_grid_matrix_periodic, no periodic axis: those of
+// ks_host_grid_matrix_star, either by its code)
+template <class H>
+void host_matrix_star_periodic_entry(const std::string& who, int ndim, const int64_t* dims, int radius, const void* taps, const void* pot,
+                                     const int* periodic, const void* wrap, int64_t* rowptr, int32_t* colidx, void* val, int64_t cap,
+                                     int64_t* nnz) {
+  Shape s = check<H>(who, ndim, dims, taps, pot, radius);
+  if (radius == 1) {
+    const Wrap<H> W = check_wrap<H>(who, s, ndim, taps, periodic, wrap);
+    host_matrix<H>(who, s, ndim, static_cast<const H*>(taps), static_cast<const H*>(pot), W, rowptr, colidx, static_cast<H*>(val), cap, nnz);
+  } else {
+    const WrapStar<H> W = check_wrap_star<H>(who, s, ndim, radius, taps, periodic, wrap);
+    host_matrix_star<H>(who, s, ndim, radius, static_cast<const H*>(taps), static_cast<const H*>(pot), W, rowptr, colidx,
+                        static_cast<H*>(val), cap, nnz);
+  }
 }
 
 // the tile the kernels of an operator are launched with (ksd::GridTile; var: with a coefficient)
 struct Tile {
   int64_t tx, ty;
 };
-template <class D> Tile tile(const Shape& s, int radius, bool var) {
+inline Tile tile_of(const Shape& s, bool half) {
   auto of = [&](auto tl) { return s.ny == 1 ? Tile{decltype(tl)::WX, 1} : Tile{decltype(tl)::TX, decltype(tl)::TY}; };
-  return ksd::grid_half(sizeof(D), radius, var) ? of(ksd::GridTile<true>{}) : of(ksd::GridTile<false>{});
+  return half ? of(ksd::GridTile<true>{}) : of(ksd::GridTile<false>{});
 }
+template <class D> Tile tile(const Shape& s, int radius, bool var) { return tile_of(s, ksd::grid_half(sizeof(D), radius, var)); }
 // The launch shape: the tiles along x and y, and the z-ranges -- as many as fill kGridWant work items, of at least
 // kGridMinZ * radius planes each.
 struct Plan {
@@ -710,11 +1045,14 @@ template <class D> struct GridOpBase : ks_operator {
 
   // ctx, sizes, element type and the launch shape (geometry into g)
   void init(ks_ctx* c, const std::string& who, const grid::Shape& s, int radius, bool var, ksd::GridGeom& g) {
+    init(c, who, s, radius, grid::tile<D>(s, radius, var), g);
+  }
+  void init(ks_ctx* c, const std::string& who, const grid::Shape& s, int radius, grid::Tile tile, ksd::GridGeom& g) {
     ctx = c;
     n_local = s.n;
     nnz = s.nnz;
     dtype = sizeof(D) == 8 ? KS_F64 : KS_C64;
-    const grid::Plan p = grid::plan(who, s, grid::tile<D>(s, radius, var), radius);
+    const grid::Plan p = grid::plan(who, s, tile, radius);
     g = p.g;
     nitems = p.nitems;
     wide = s.ny == 1;
@@ -752,8 +1090,9 @@ template <class D> struct GridOp : GridOpBase<D> {
   using GridOpBase<D>::ctx; using GridOpBase<D>::diag; using GridOpBase<D>::nitems; using GridOpBase<D>::wide;
   ksd::GridPerDev<D> g{};   // (the open operator's kernel takes its GridDev part)
   bool periodic = false;  // some axis wraps: the kernel's periodic instantiation
-  int radius = 1;      // > 1: the star stencil, k_grid_star with the taps of `star`
+  int radius = 1;      // > 1: the star stencil, k_grid_star with the taps of `star` (k_grid_star_per where some axis wraps)
   D star[25] = {};     // its 6 radius + 1 slots
+  D starw[24] = {};    // ... and the wrap values of its 6 radius links
   void launch(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma) override {
     using TL = ksd::GridTileOf<D>;
     const ksd::GridDev<D>& go = g;
@@ -767,6 +1106,17 @@ template <class D> struct GridOp : GridOpBase<D> {
     else ksd::k_grid<D, TL::TX, TL::TY, ksd::GridDev<D>><<<nitems, kBlock, 0, ctx->stream>>>(go, x, diag, y, st, shifted, theta, sigma);
   }
   template <int R> void launch_star(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma) {
+    if (periodic) {
+      using TP = ksd::GridTile<ksd::grid_star_per_half(sizeof(D), R)>;
+      ksd::GridStarPerDev<D, R> gp;
+      static_cast<ksd::GridGeom&>(gp) = g;
+      for (int k = 0; k < 6 * R + 1; ++k) gp.tap[k] = star[k];
+      for (int k = 0; k < 6 * R; ++k) gp.wrap[k] = starw[k];
+      gp.px = g.px; gp.py = g.py; gp.pz = g.pz;
+      if (wide) ksd::k_grid_star_per<D, TP::WX, 1, R><<<nitems, kBlock, 0, ctx->stream>>>(gp, x, diag, y, st, shifted, theta, sigma);
+      else ksd::k_grid_star_per<D, TP::TX, TP::TY, R><<<nitems, kBlock, 0, ctx->stream>>>(gp, x, diag, y, st, shifted, theta, sigma);
+      return;
+    }
     using TL = ksd::GridTileOf<D, R>;
     ksd::GridStarDev<D, R> gs;
     static_cast<ksd::GridGeom&>(gs) = g;
@@ -781,25 +1131,30 @@ ks_operator* make_grid(ks_ctx* ctx, const std::string& who, int ndim, const int6
                        const int* periodic, const void* wrap, int radius = 1) {
   using H = typename HostT<D>::type;
   grid::Shape s = grid::check<H>(who, ndim, dims, taps, potential, radius);
-  KS_REQUIRE(radius == 1 || !periodic, KS_ERR_ARGUMENT, who + ": periodic axes take radius 1");
-  const grid::Wrap<H> W = grid::check_wrap<H>(who, s, ndim, taps, periodic, wrap);
   auto op = std::make_unique<GridOp<D>>();
   H t[7], centre;
+  bool half = ksd::grid_half(sizeof(D), radius, false);
   if (radius == 1) {
+    const grid::Wrap<H> W = grid::check_wrap<H>(who, s, ndim, taps, periodic, wrap);
     grid::seven_taps(ndim, static_cast<const H*>(taps), t);
     std::memcpy(op->g.tap, t, sizeof(t));
     centre = t[3];
+    std::memcpy(op->g.wrap, W.w, sizeof(W.w));
+    op->g.px = W.per[0]; op->g.py = W.per[1]; op->g.pz = W.per[2];
+    op->periodic = W.any();
   } else {
+    const grid::WrapStar<H> W = grid::check_wrap_star<H>(who, s, ndim, radius, taps, periodic, wrap);
     H ts[25];
     grid::star_taps(ndim, radius, static_cast<const H*>(taps), ts);
     std::memcpy(op->star, ts, sizeof(ts));
     centre = ts[3 * radius];
+    std::memcpy(op->starw, W.w, sizeof(W.w));
+    op->g.px = W.per[0]; op->g.py = W.per[1]; op->g.pz = W.per[2];
+    op->periodic = W.any();
+    if (op->periodic) half = ksd::grid_star_per_half(sizeof(D), radius);
   }
   op->radius = radius;
-  std::memcpy(op->g.wrap, W.w, sizeof(W.w));
-  op->g.px = W.per[0]; op->g.py = W.per[1]; op->g.pz = W.per[2];
-  op->periodic = W.any();
-  op->init(ctx, who, s, radius, false, op->g);
+  op->init(ctx, who, s, radius, grid::tile_of(s, half), op->g);
   op->upload_diag(centre, potential);
   return op.release();
 }

@@ -428,6 +428,12 @@ int ks_operator_grid_star(ks_ctx* ctx, int ndim, const int64_t* dims, int radius
   });
 }
 
+int ks_operator_grid_star_periodic(ks_ctx* ctx, int ndim, const int64_t* dims, int radius, int dtype, const void* taps,
+                                   const void* potential, const int* periodic, const void* wrap, ks_operator** out) {
+  return grid_operator_entry(ctx, dtype, out, "ks_operator_grid_star_periodic", [&](auto d, const std::string& who) {
+    return make_grid<decltype(d)>(ctx, who, ndim, dims, taps, potential, periodic, wrap, radius);
+  });
+}
 int ks_operator_grid_periodic(ks_ctx* ctx, int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential,
                               const int* periodic, const void* wrap, ks_operator** out) {
   return grid_operator_entry(ctx, dtype, out, "ks_operator_grid_periodic", [&](auto d, const std::string& who) {
@@ -1650,6 +1656,13 @@ int ks_host_grid_matrix_star(int ndim, const int64_t* dims, int radius, int dtyp
   });
 }
 
+int ks_host_grid_matrix_star_periodic(int ndim, const int64_t* dims, int radius, int dtype, const void* taps, const void* potential,
+                                      const int* periodic, const void* wrap, int64_t* rowptr, int32_t* colidx, void* val, int64_t cap,
+                                      int64_t* nnz) {
+  return grid_host_entry(dtype, "ks_host_grid_matrix_star_periodic", [&](auto h, const std::string& who) {
+    grid::host_matrix_star_periodic_entry<decltype(h)>(who, ndim, dims, radius, taps, potential, periodic, wrap, rowptr, colidx, val, cap, nnz);
+  });
+}
 int ks_host_grid_matrix_periodic(int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential, const int* periodic,
                                  const void* wrap, int64_t* rowptr, int32_t* colidx, void* val, int64_t cap, int64_t* nnz) {
   return grid_host_entry(dtype, "ks_host_grid_matrix_periodic", [&](auto h, const std::string& who) {

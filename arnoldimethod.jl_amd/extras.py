@@ -201,7 +201,7 @@ def b_orthonormal_operator(A, L, ctx: api.Context | None = None):
     return op, back
 
 
-def bloch_wrap(taps, theta) -> np.ndarray:
+def bloch_wrap(taps, theta, radius=1) -> np.ndarray:
     """The `wrap` array of `api.grid_operator(..., periodic=..., wrap=...)` for Bloch boundary conditions: the link that leaves the
     cell in the + direction of axis a carries t_{+a} e^{+i theta_a}, the one in the - direction t_{-a} e^{-i theta_a} (a band
     structure at the k-point theta_a = k_a L_a).  `taps`: the 2 ndim + 1 taps in ascending column order; `theta`: one phase per axis
@@ -214,18 +214,29 @@ def bloch_wrap(taps, theta) -> np.ndarray:
         taps, diagonal = diffusion_terms(shape, coeff, spacing, V, periodic=True)
         op = api.grid_variable_operator(shape, taps, coeff, diagonal, periodic=True, wrap=bloch_wrap(taps, theta))
 
-    -- exactly Hermitian for a real `coeff`; the diagonal does not depend on theta (|hw| = |h|)."""
+    -- exactly Hermitian for a real `coeff`; the diagonal does not depend on theta (|hw| = |h|).
+
+    `radius` = R (never inferred from the length of `taps`): the 2 ndim R + 1 taps of a star stencil, for
+    `api.grid_star_operator(shape, taps, R, ..., periodic=True, wrap=bloch_wrap(taps, theta, radius=R))`.  Returns 2 ndim R values
+    in the order of the taps without the centre: every +-d link of axis a carries t e^{+-i theta_a}, the same phase at every
+    distance d, because a link crosses the cell boundary at most once."""
     t = np.asarray(taps)
     th = np.atleast_1d(np.asarray(theta, dtype=np.float64))
-    if t.ndim != 1 or t.size not in (3, 5, 7):
-        raise api.DimensionMismatch(f"taps must hold 3, 5 or 7 values, got shape {t.shape}")
-    ndim = (t.size - 1) // 2
+    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= 4:
+        raise api.ArgumentError(f"radius must be an integer in 1...4, got {radius!r}")
+    R = int(radius)
+    if t.ndim != 1 or t.size not in (2 * R + 1, 4 * R + 1, 6 * R + 1):
+        raise api.DimensionMismatch(f"taps must hold {2 * R + 1}, {4 * R + 1} or {6 * R + 1} values"
+                                    f"{'' if R == 1 else f' at radius {R}'}, got shape {t.shape}")
+    ndim = (t.size - 1) // (2 * R)
     if th.shape != (ndim,):
         raise api.DimensionMismatch(f"theta takes one phase per axis ({ndim}), got shape {th.shape}")
-    w = np.empty(2 * ndim, dtype=np.complex128)
+    w = np.empty(2 * ndim * R, dtype=np.complex128)
+    c = ndim * R
     for a in range(ndim):
-        w[ndim - 1 - a] = t[ndim - 1 - a] * np.exp(-1j * th[a])
-        w[ndim + a] = t[ndim + 1 + a] * np.exp(1j * th[a])
+        for d in range(1, R + 1):
+            w[c - a * R - d] = t[c - a * R - d] * np.exp(-1j * th[a])
+            w[c + a * R + d - 1] = t[c + a * R + d] * np.exp(1j * th[a])
     return w
 
 

@@ -267,14 +267,16 @@ end
 # each).  `wrap`: 2 ndim values in the order of the taps without the centre ([-z, -y, -x, +x, +y, +z] in 3-D), the entries of the links
 # that cross the cell boundary; `nothing` = the taps (plain periodicity), t e^{+-i theta} = Bloch, -taps = antiperiodic.
 # `radius` = 2, 3, 4: a star stencil with neighbours at the distances 1...radius along every axis (ks_operator_grid_star: central
-# differences of order 4, 6, 8), open boundaries only; `taps` then holds 2 ndim radius + 1 values in ascending column order,
-# [-R z ... -1 z, -R y ... -1 y, -R x ... -1 x, centre, +1 x ... +R x, +1 y ... +R y, +1 z ... +R z] in 3-D.
+# differences of order 4, 6, 8); `taps` then holds 2 ndim radius + 1 values in ascending column order,
+# [-R z ... -1 z, -R y ... -1 y, -R x ... -1 x, centre, +1 x ... +R x, +1 y ... +R y, +1 z ... +R z] in 3-D.  With `periodic` or `wrap` as well
+# (ks_operator_grid_star_periodic): a periodic axis needs an extent of at least 2 radius + 1, and `wrap` holds 2 ndim radius values in the
+# order of the taps without the centre -- the entry of the link of that direction and distance where it crosses the cell boundary
+# (Bloch: t e^{+-i theta_a}, the same phase at every distance).
 function HipGridOperator(ctx::HipContext, dims::NTuple{N,Integer}, taps::AbstractVector; potential::Union{Nothing,AbstractArray} = nothing,
                          periodic::Union{Nothing,Bool,NTuple{N,Bool},AbstractVector{Bool}} = nothing,
                          wrap::Union{Nothing,AbstractVector} = nothing, radius::Integer = 1) where {N}
     1 <= N <= 3 || throw(ArgumentError("a grid has 1, 2 or 3 dimensions"))
     1 <= radius <= 4 || throw(ArgumentError("radius must be 1, 2, 3 or 4"))
-    (radius == 1 || (periodic === nothing && wrap === nothing)) || throw(ArgumentError("periodic / wrap take radius 1"))
     T = (eltype(taps) <: Complex || (potential !== nothing && eltype(potential) <: Complex) || (wrap !== nothing && eltype(wrap) <: Complex)) ? ComplexF64 : Float64
     length(taps) == 2N * radius + 1 || throw(DimensionMismatch("a $(N)-D grid of radius $(radius) takes $(2N * radius + 1) taps"))
     n = prod(Int64.(dims))
@@ -285,8 +287,17 @@ function HipGridOperator(ctx::HipContext, dims::NTuple{N,Integer}, taps::Abstrac
     if periodic !== nothing || wrap !== nothing
         flags = periodic === nothing ? fill(Cint(0), N) : periodic isa Bool ? fill(Cint(periodic), N) : Cint[periodic...]
         length(flags) == N || throw(DimensionMismatch("periodic takes one flag per axis ($(N))"))
-        (wrap === nothing || length(wrap) == 2N) || throw(DimensionMismatch("a $(N)-D grid takes $(2N) wrap values"))
+        (wrap === nothing || length(wrap) == 2N * radius) || throw(DimensionMismatch("a $(N)-D grid of radius $(radius) takes $(2N * radius) wrap values"))
         w = wrap === nothing ? T[] : Vector{T}(wrap)
+        if radius > 1
+            GC.@preserve d t v flags w begin
+                check(ccall((:ks_operator_grid_star_periodic, LIB), Cint,
+                            (Ptr{Cvoid}, Cint, Ptr{Int64}, Cint, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cint}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),
+                            ctx.h, Cint(N), pointer(d), Cint(radius), dtype_code(T), pointer(t), potential === nothing ? C_NULL : pointer(v),
+                            pointer(flags), wrap === nothing ? C_NULL : pointer(w), r))
+            end
+            return _finish_operator(T, r[], n, ctx, nothing)
+        end
         GC.@preserve d t v flags w begin
             check(ccall((:ks_operator_grid_periodic, LIB), Cint,
                         (Ptr{Cvoid}, Cint, Ptr{Int64}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cint}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),

@@ -274,10 +274,44 @@ int ks_operator_grid_periodic(ks_ctx* ctx, int ndim, const int64_t* dims /* ndim
  *   product     every product rounded on its own and added to +0.0 in this order: bit-identical to ks_operator_csr of the matrix.
  *               An absent tap -- outside the grid, or beyond the radius -- is not multiplied at all
  * KS_ERR_ARGUMENT in addition: radius outside 1...4 (the message names radius); "tap k is not finite" counts k in this layout.
- * Periodic axes take radius 1 (ix).  With radius == 1 the operator is that of ks_operator_grid: same matrix, same kernel. */
+ * Boundaries are open here; periodic axes: (x-b).  With radius == 1 the operator is that of ks_operator_grid: same matrix, same
+ * kernel. */
 int ks_operator_grid_star(ks_ctx* ctx, int ndim, const int64_t* dims /* ndim entries: nx[, ny[, nz]] */, int radius, int dtype,
                           const void* taps /* 2*ndim*radius+1 values of dtype */,
                           const void* potential /* n values of dtype, or NULL */, ks_operator** out);
+/* (x-b) ... the STAR stencil with periodic axes: crystals and supercells with central differences of order 4, 6, 8, a band structure
+ * at a k-point with an 8th-order Laplacian -- mul!(y, A, x), src/expansion.jl:121, still with nothing stored per non-zero and the
+ * same compulsory traffic.  Everything of (viii) and (x) holds, with these additions.  DEFINITION -- the operator is the matrix
+ * ks_host_grid_matrix_star_periodic returns:
+ *   periodic    as in (ix): ndim flags in the order of dims, NULL: no axis wraps.  On a periodic axis of extent m the point at
+ *               index i has its +d neighbour at i + d - m where i + d >= m and its -d neighbour at i - d + m where i < d; an axis
+ *               that does not wrap is truncated as in (x) and may have any extent >= 1
+ *   extent      of a periodic axis: at least 2 R + 1 (below that two links of a row coincide or a link is a self-link)
+ *   wrap        2 ndim R values of `dtype` in the order of the taps with the centre left out: in 3-D
+ *                 [-R z ... -1 z, -R y ... -1 y, -R x ... -1 x, +1 x ... +R x, +1 y ... +R y, +1 z ... +R z]
+ *               -- the entry of the link of that direction and distance where it crosses the cell boundary.  NULL: the taps
+ *               themselves (plain periodicity).  Bloch: wrap[+-d a] = t e^{+-i theta_a}, the same phase at every distance (a link
+ *               crosses the boundary at most once; extras.bloch_wrap(taps, theta, radius)).  Values of axes that do not wrap are
+ *               neither read nor checked
+ *   row         columns ascending.  Before the centre the axes come in the order z, y, x, each with two groups: (1) its +d links
+ *               that wrap (i_a + d >= m_a), d ascending, column r + (d - m_a) stride_a, value wrap[+d a]; (2) its interior -d
+ *               links, d = R ... 1, value tap[-d a].  Then the centre.  After it the axes come in the order x, y, z, each with two
+ *               groups: (1) its interior +d links, d = 1 ... R; (2) its -d links that wrap (i_a - d < 0), d = R ... 1, column
+ *               r + (m_a - d) stride_a, value wrap[-d a].  With m_a >= 2 R + 1 this is the ascending column order; a row of a fully
+ *               periodic grid has exactly 6 R + 1 entries (2 ndim R + 1).  As in (ix) a wrap link stands (and is summed) at another
+ *               place than the interior link of its direction
+ *   product     every product rounded on its own and added to +0.0 in this order: bit-identical to ks_operator_csr of the matrix
+ *   nnz         n + sum over the axes a of (periodic ? 2 R n : sum over d = 1...R of 2 max(m_a - d, 0) n / m_a): what
+ *               ks_operator_size reports
+ * With tap[-d a] = conj(tap[+d a]) and wrap[-d a] = conj(wrap[+d a]) the matrix is exactly Hermitian.  KS_ERR_ARGUMENT in addition:
+ * a periodic axis of extent < 2 R + 1 (the message names the axis, the extent, the radius and the word "periodic"), a non-finite
+ * wrap value of a periodic axis ("wrap value k is not finite", k its index in `wrap`).  REDUCTIONS -- with no periodic axis the
+ * operator is that of ks_operator_grid_star (same object, same kernel launch), with radius == 1 that of ks_operator_grid_periodic. */
+int ks_operator_grid_star_periodic(ks_ctx* ctx, int ndim, const int64_t* dims /* ndim entries: nx[, ny[, nz]] */, int radius, int dtype,
+                                   const void* taps /* 2*ndim*radius+1 values of dtype */,
+                                   const void* potential /* n values of dtype, or NULL */,
+                                   const int* periodic /* ndim flags, or NULL */,
+                                   const void* wrap /* 2*ndim*radius values of dtype, or NULL */, ks_operator** out);
 /* (xi) ... with a VARIABLE coefficient: A = -div(c(x) grad) + V(x) -- heterogeneous diffusion, a position-dependent effective mass,
  * div (1 / eps) grad in photonics, variable-density acoustics -- mul!(y, A, x), src/expansion.jl:121, still with nothing stored per
  * non-zero although the off-diagonal entries vary from link to link: the coefficient is cell-centred, one Float64 per grid point, and
@@ -777,6 +811,14 @@ int ks_host_grid_matrix_periodic(int ndim, const int64_t* dims, int dtype, const
  * that no context is involved. */
 int ks_host_grid_matrix_star(int ndim, const int64_t* dims, int radius, int dtype, const void* taps, const void* potential,
                              int64_t* rowptr /* n+1 */, int32_t* colidx, void* val, int64_t cap, int64_t* nnz);
+/* ... and the matrix that DEFINES ks_operator_grid_star_periodic (mul!(y, A, x), src/expansion.jl:121): `radius`, `taps`, `periodic`
+ * and the 2 ndim radius `wrap` values as there, every row in the order of (x-b), *nnz = n + sum over the axes a of
+ * (periodic ? 2 radius n : sum over d = 1...radius of 2 max(m_a - d, 0) n / m_a) (also reported when cap is too small).  With no
+ * periodic axis the arrays are those of ks_host_grid_matrix_star, with radius == 1 those of ks_host_grid_matrix_periodic.  Same
+ * refusals as that operator, except that no context is involved. */
+int ks_host_grid_matrix_star_periodic(int ndim, const int64_t* dims, int radius, int dtype, const void* taps, const void* potential,
+                                      const int* periodic /* ndim flags, or NULL */, const void* wrap /* 2*ndim*radius values, or NULL */,
+                                      int64_t* rowptr /* n+1 */, int32_t* colidx, void* val, int64_t cap, int64_t* nnz);
 /* ... and the matrix that DEFINES ks_operator_grid_var (mul!(y, A, x), src/expansion.jl:121): `coeff` as there, the off-diagonal entries
  * fl(0.5 t_k * fl(c[r] + c[s])), every row a sub-sequence of the 7 slots, *nnz as for ks_host_grid_matrix (also reported when cap is
  * too small).  With c == 1 the arrays are those of ks_host_grid_matrix.  Same refusals as that operator, except that no context is

@@ -19,7 +19,12 @@ Float64, 7-point -Laplacian (+ a harmonic potential) on m x m x m grids.  Per si
                (f) csr_operator(host_grid_matrix(..., periodic=True))       the same matrix stored
              --radius R (2, 3, 4; ks_operator_grid_star) runs (a), (b) and (c) with the star stencil of central differences of
              order 2 R, extras.fd_laplacian_taps(3, 2 R), instead of the 7-point one: (a) and (c) still move 24 n / 16 n bytes,
-             (b) streams the 6 R + 1 entries of a row.  (d) and --periodic belong to the 7-point stencil and are left out.
+             (b) streams the 6 R + 1 entries of a row.  (d) belongs to the 7-point stencil and is left out.  With --periodic as
+             well (ks_operator_grid_star_periodic), on the torus:
+               (a) the open star operator with the potential                                     24 n bytes
+               (e) grid_star_operator(..., periodic=True) with the potential                     24 n bytes, as (a)
+               (f) csr_operator(host_grid_star_matrix(..., periodic=True))                       the same matrix stored
+             in the same rounds, and the solve on (e) and (f).
              --variable (ks_operator_grid_var) runs the variable-coefficient operator -div(c grad) + V, c a smooth field with a jump
              (extras.diffusion_terms, Dirichlet), in the same rounds as today's constant-coefficient operator, the floor:
                (a) grid_variable_operator with the diagonal        32 n bytes
@@ -41,7 +46,8 @@ Float64, 7-point -Laplacian (+ a harmonic potential) on m x m x m grids.  Per si
                (e) grid_box_operator(..., periodic=True) with the potential                      24 n bytes, as (a)
                (f) csr_operator(host_grid_box_matrix(..., periodic=True))                        the same matrix stored
              in the same rounds as the open box operator (a), and the solve on (e) and (f) too.
-             --complex runs the grid operators of the run that the other switches select -- (a) and (c); --periodic: (e) alone;
+             --complex runs the grid operators of the run that the other switches select -- (a) and (c); --periodic: (e) alone
+             (--radius R --periodic: (e) of the star stencil with Bloch wrap values at theta = (0.7, 1.1, 1.9));
              --variable: (a), (c), (d); --variable --periodic: (e) alone, at the k-point theta = (0.7, 1.1, 1.9) (Bloch wrap values) -- in the same rounds with ComplexF64 taps, potential and vectors (twice the bytes; c stays
              Float64): products only, no stored matrix and no solve.  --wide puts them on the m^2 x 1 x m grid, which takes the
              one-row tiles.
@@ -235,30 +241,41 @@ def report(out, prod, m, n, args):
 
 
 def main_star(args):
-    """--radius R: (a), (b), (c) with the star stencil of central differences of order 2 R."""
+    """--radius R: (a), (b), (c) with the star stencil of central differences of order 2 R; with --periodic (a), the operator on
+    the torus (e) and its stored matrix (f), and the solve on (e) and (f)."""
     from arnoldimethod_jl_amd import extras
 
     R = args.radius
-    if R not in (2, 3, 4) or args.periodic:
-        raise SystemExit("--radius takes 2, 3 or 4 and no --periodic")
+    if R not in (2, 3, 4):
+        raise SystemExit("--radius takes 2, 3 or 4")
     taps = extras.fd_laplacian_taps(3, 2 * R)
     ctx = ks.Context(0)
     for m in (int(s) for s in args.sizes.split(",")):
         shape, n = (m, m, m), m ** 3
         V = ks.matrices.harmonic_potential(shape)
         t0 = time.perf_counter()
-        A = ks.host_grid_matrix(shape, taps, V, radius=R)
-        ops = {
-            "a_grid_potential": ks.grid_operator(shape, taps, V, ctx=ctx, radius=R),
-            "b_stored_potential": ks.csr_operator(A, ctx),
-            "c_grid_plain": ks.grid_operator(shape, taps, ctx=ctx, radius=R),
-        }
+        if args.periodic:
+            A = ks.host_grid_star_matrix(shape, taps, R, V, periodic=True)
+            stored, solve = "f_stored_star_periodic", ("e_star_periodic", "f_stored_star_periodic")
+            ops = {
+                "a_grid_potential": ks.grid_operator(shape, taps, V, ctx=ctx, radius=R),
+                "e_star_periodic": ks.grid_star_operator(shape, taps, R, V, ctx=ctx, periodic=True),
+                stored: ks.csr_operator(A, ctx),
+            }
+        else:
+            A = ks.host_grid_matrix(shape, taps, V, radius=R)
+            stored, solve = "b_stored_potential", ("a_grid_potential", "b_stored_potential")
+            ops = {
+                "a_grid_potential": ks.grid_operator(shape, taps, V, ctx=ctx, radius=R),
+                stored: ks.csr_operator(A, ctx),
+                "c_grid_plain": ks.grid_operator(shape, taps, ctx=ctx, radius=R),
+            }
         nnz = A.nnz
         setup_s = time.perf_counter() - t0
         del A
-        fmt = {"b_stored_potential": ops["b_stored_potential"].format}
-        by = {"a_grid_potential": 24.0 * n, "c_grid_plain": 16.0 * n, "b_stored_potential": fmt["b_stored_potential"]["bytes_per_nnz"] * nnz + 16.0 * n}
-        out = dict(m=m, n=n, radius=R, nnz=nnz, setup_seconds=round(setup_s, 2), formats=fmt, chains=args.chains, products_per_round=args.chains * MAXDIM)
+        fmt = {stored: ops[stored].format}
+        by = {"a_grid_potential": 24.0 * n, "c_grid_plain": 16.0 * n, "e_star_periodic": 24.0 * n, stored: fmt[stored]["bytes_per_nnz"] * nnz + 16.0 * n}
+        out = dict(m=m, n=n, radius=R, periodic=args.periodic, nnz=nnz, setup_seconds=round(setup_s, 2), formats=fmt, chains=args.chains, products_per_round=args.chains * MAXDIM)
         prod = bench_products(ctx, ops, n, args.rounds, args.chains)
         for name, s in prod.items():
             s["bytes_per_product"] = by[name]
@@ -266,7 +283,7 @@ def main_star(args):
             s["hbm_fraction_of_kernels"] = by[name] / (s["event_us"] * 1e-6) / PEAK
         out["us_per_product"] = prod
         if not args.no_solve:
-            runs = {name: Solve(ctx, ops[name], n) for name in ("a_grid_potential", "b_stored_potential")}
+            runs = {name: Solve(ctx, ops[name], n) for name in solve}
             for s in runs.values():
                 s.cycles(3)
             rate = {name: [] for name in runs}
@@ -274,7 +291,7 @@ def main_star(args):
                 for name, s in runs.items():
                     rate[name].append(s.cycles(args.cycles))
             out["iterations_per_s"] = {name: stats(v) for name, v in rate.items()}
-            out["same_restart_trail"] = runs["a_grid_potential"].trail == runs["b_stored_potential"].trail
+            out["same_restart_trail"] = runs[solve[0]].trail == runs[solve[1]].trail
             out["blocks"] = {name: s.ws.sstep_info["blocks"] for name, s in runs.items()}
             for s in runs.values():
                 s.ws.close()
@@ -423,8 +440,8 @@ def main_complex(args):
     from arnoldimethod_jl_amd import extras
 
     R = 1 if args.radius is None else args.radius
-    if R not in (1, 2, 3, 4) or (R > 1 and (args.periodic or args.variable)):
-        raise SystemExit("--complex takes one of --periodic, --radius 2 / 3 / 4 and --variable (or --variable --periodic)")
+    if R not in (1, 2, 3, 4) or (R > 1 and args.variable):
+        raise SystemExit("--complex takes one of --periodic, --radius 2 / 3 / 4 (or --radius R --periodic) and --variable (or --variable --periodic)")
     phase = 1.0 + 0.25j
     ctx = ks.Context(0)
     for m in (int(s) for s in args.sizes.split(",")):
@@ -447,6 +464,12 @@ def main_complex(args):
                 "d_grid_potential": ks.grid_operator(shape, phase * LAPLACE, V, ctx=ctx),
             }
             by = {"a_var_diagonal": 56.0 * n, "c_var_plain": 40.0 * n, "d_grid_potential": 48.0 * n}
+        elif args.periodic and R > 1:            # the star stencil at a k-point: Hermitian, every wrap value complex
+            taps = extras.fd_laplacian_taps(3, 2 * R)
+            per = tuple(e >= 2 * R + 1 for e in shape)
+            ops = {"e_star_periodic": ks.grid_star_operator(shape, taps, R, V.real, ctx=ctx, periodic=per,
+                                                            wrap=extras.bloch_wrap(taps, (0.7, 1.1, 1.9), radius=R))}
+            by = {"e_star_periodic": 48.0 * n}
         elif args.periodic:
             ops = {"e_grid_periodic": ks.grid_operator(shape, phase * LAPLACE, V, ctx=ctx, periodic=tuple(e >= 3 for e in shape))}
             by = {"e_grid_periodic": 48.0 * n}
