@@ -64,6 +64,7 @@ template <class D> struct CsrOp : ks_operator {
   void* smask2 = nullptr;    // == smask (the array is padded to an even number of rows): masks of rows 2t, 2t+1 in one word
   ksd::StencilDict<D> sdict{};
   int nstencil_local = 0;            // leading slots of the stencil dictionary; the rest name ghost columns only
+  StencilGeom geom;                  // Float64, no ghosts: are the masks the box rule of a grid (ks_stencil_geom.hpp)
   mutable bool split_said = false;   // (KS_DIST_SPLIT_DEBUG: one line per operator)
   // sliced-ELLPACK layout (k_spmv_sell): slices of 64 rows, column-major, padded to the slice's longest row
   void* sliceptr = nullptr;  // entry offsets of the slices, same integer type as rowptr
@@ -174,6 +175,24 @@ template <class D> struct CsrOp : ks_operator {
         const int zmarch = env_int("KS_MARCH_Z", 1), zr_env = env_int("KS_MARCH_ZR", 0);
         const int64_t Pz = sdict.delta[6];
         if (shape && zmarch && sdict.delta[0] == -Pz && (Pz & 1) == 0 && Pz >= 8 * 8 * 512) {
+          // ... and where the masks are the box rule of the grid (ks_stencil_geom.hpp), the form that derives them from the row
+          // number instead of streaming them and takes the +P tap one step late (k_spmv_stencil_marchg): 33.1-33.8 us against
+          // 37.8-38.7 in the solver's chain (profiles/stencil_geom.txt).  Tiles of 1 024 in-plane offsets on 512 threads (of the
+          // widths 512 / 1 024 / 2 048 the one that measured fastest; four workgroups per CU by their window buffers); z-ranges so
+          // that the resident workgroup slots of an XCD (32 CUs) are filled twice, at least four planes each.
+          // KS_MARCH_GEOM=0 selects the form that reads the masks.
+          if (geom.box && n_local / Pz >= 8 && env_int("KS_MARCH_GEOM", 1) != 0) {
+            constexpr int kTileG = 1024, kThreadsG = 512, kSlotsG = 2 * 32 * 4;
+            const int nzp = (int)(n_local / Pz), cmax = (int)(((Pz + kTileG - 1) / kTileG + 7) / 8);
+            int nzr = zr_env > 0 ? zr_env : std::max(1, (kSlotsG + cmax / 2) / cmax);
+            nzr = std::max(1, std::min(nzr, nzp / 4));
+            auto gg = [&](auto odd_tag) {
+              ksd::k_spmv_stencil_marchg<decltype(odd_tag)::value, kTileG, kThreadsG><<<8 * cmax * nzr, kThreadsG, 0, s>>>(m2, sdict, x, y, n_local, nzr, st, sh, shift_theta, shift_sigma);
+            };
+            if (odd == 0x14u) gg(std::integral_constant<unsigned, 0x14u>{});   // (a box grid: +-1 odd, +-nx odd with nx)
+            else gg(std::integral_constant<unsigned, 0x36u>{});
+            return;
+          }
           const int nzp = (int)((n_local + Pz - 1) / Pz), cmax = (int)(((Pz + 511) / 512 + 7) / 8);
           int nzr = zr_env > 0 ? zr_env : std::max(1, (288 + cmax / 2) / cmax);
           nzr = std::max(1, std::min(nzr, nzp / 4));
@@ -634,6 +653,9 @@ CsrOp<D>* upload(ks_ctx* ctx, const CsrPlan<D>& P, int64_t nrows, int64_t nnz, c
       if (P.stencil_mask_bytes == 1) op->smask = upload_vec(P.mask8, pad, true);
       else op->smask = upload_vec(P.mask32, pad, true);
       op->smask2 = op->smask;
+      // (the masks stay uploaded: the clamped edge path and every other kernel read them)
+      if (std::is_same<D, double>::value && P.stencil_mask_bytes == 1 && P.nstencil == P.nstencil_local)
+        op->geom = stencil_geometry(P.sdelta.data(), P.nstencil, nrows, P.mask8.data(), P.mask8.size());
       break;
     }
     case KS_LAYOUT_DVI:

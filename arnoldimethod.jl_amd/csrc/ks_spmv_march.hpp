@@ -637,4 +637,237 @@ __global__ void __launch_bounds__(TW)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// ------------------------------------------------------------------------------------------------------------------------
+// Z-MARCHING form WITHOUT A MASK STREAM, for a box grid whose masks are implied by the geometry (ks_stencil_geom.hpp: slots
+// (-P, -nx, -1, 0, +1, +nx, +P), every row's mask the box rule, n a whole number of planes).  The in-plane offset of a lane's
+// rows is constant along the march, so the five near-tap bits of each row are derived ONCE, before the loop (per row: with odd nx
+// a pair straddles two grid lines); the two far bits are wave-uniform per plane (z > 0, z < nz - 1).
+//   The +P tap comes LATE: step z reads only the window of plane z, adds the slots -P ... +nx of its own rows (-P: the own pair
+// of the step before, kept in registers) and finishes the rows of plane z - 1 with their last slot -- x[r + P] is the own pair it
+// has just read -- the shift epilogue and the store.  Same products, same order of additions as every other form: bit-identical.
+// A step then waits for ONE window, the one issued two steps earlier; the window of plane z + 1 stays in flight across it.  A
+// wave's vector-memory queue per step is [window pieces of plane z + 2][stores of plane z - 1], nothing else, and windows past
+// the end of the z-range are not issued at all.
+//   TILE: in-plane offsets per workgroup (512, 1 024, 2 048; the window is TILE + 512 rows: 2x, 1.5x, 1.25x its tile), TW threads,
+//   TILE / (2 TW) pairs per lane; three window buffers.  Edge steps (windows that leave [0, n)) and work items as in
+//   k_spmv_stencil_marchz; they and only they read the masks.
+__device__ __forceinline__ void march_wait_vm(int c) {   // c wave-uniform
+  switch (c) {
+    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
+    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
+    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
+    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
+    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
+    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
+    default: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;   // (waiting for more than needed is always safe)
+  }
+}
+
+template <unsigned ODDM, int TILE, int TW>
+__global__ void __launch_bounds__(TW)
+    k_spmv_stencil_marchg(const uint16_t* __restrict__ mask2, const StencilDict<double> d, const double* __restrict__ x,
+                          double* __restrict__ y, int64_t n, int nzr, const DevState* __restrict__ st, int shifted, double theta,
+                          double sigma) {
+  constexpr int NSLOT = 7, KOWN = 3, KFM = 0, KFP = 6;
+  constexpr unsigned NEARM = 0x3eu;
+  constexpr int PPL = TILE / (2 * TW), kWinB = (TILE + 512) * 8, kPieces = (TILE + 512) / 128, kWaves = TW / 64;
+  constexpr int kRounds = (kPieces + kWaves - 1) / kWaves;
+  static_assert(TW == 256 || TW == 512, "four or eight waves");
+  static_assert((PPL == 1 || PPL == 2) && PPL * 2 * TW == TILE, "one or two pairs per lane");
+  static_assert(3 * kWinB <= 60 * 1024, "three window buffers in at most 60 KiB");
+  static_assert(kRounds + 2 * PPL <= 7, "march_wait_vm counts up to 7");
+  if (st && st->breakdown >= 0) return;
+  __shared__ __attribute__((aligned(16))) unsigned char win[3][kWinB];
+  const int64_t P = d.delta[KFP];
+  const int nx = d.delta[5], ny = (int)(P / nx);
+  const int nz = (int)(n / P), ntp = (int)((P + TILE - 1) / TILE);   // (n is a whole number of planes)
+  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+  int cnt;
+  const int tj0 = march_tile(xcd, 0, 0, 0, ntp, cnt);
+  cnt -= tj0;
+  if (cnt <= 0) return;
+  const int zr = slot / cnt, tile = tj0 + slot % cnt;
+  if (zr >= nzr) return;
+  const int za = (int)((int64_t)zr * nz / nzr), zb = (int)((int64_t)(zr + 1) * nz / nzr);
+  const int64_t off0 = (int64_t)tile * TILE;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t lane_w = (threadIdx.x & 63u) * 16u;
+  const uint32_t win0 = (uint32_t)(uintptr_t)&win[0][0];
+  const bool plain_st = (shifted & 2) != 0;
+  const int nw = (kPieces - wave + kWaves - 1) / kWaves;   // window pieces this wave copies per plane (uniform)
+  uint32_t lane_b[PPL];   // byte offset of pair j of this lane inside the tile
+  bool lane_in[PPL];      // the pair belongs to the plane (P is even)
+  bool wave_has[PPL];     // some lane of this wave has its pair j in the plane (uniform): the wave issues that store
+  int mA[PPL], mB[PPL];   // the near-tap bits (slots 1 .. 5) of the pair's two rows
+  int nst = 0;
+#pragma unroll
+  for (int j = 0; j < PPL; ++j) {
+    const int64_t o = off0 + (int64_t)j * 2 * TW + 2 * (int64_t)threadIdx.x;
+    lane_b[j] = (uint32_t)(j * 2 * TW + 2 * (int)threadIdx.x) * 8u;
+    lane_in[j] = o + 1 < P;
+    wave_has[j] = off0 + (int64_t)j * 2 * TW + 128 * (int64_t)wave + 1 < P;
+    nst += wave_has[j] ? 1 : 0;
+    const int oa = (int)o, ob = oa + 1;
+    const int ya = oa / nx, xa = oa - ya * nx, yb = ob / nx, xb = ob - yb * nx;
+    mA[j] = 0x08 | (ya > 0 ? 0x02 : 0) | (xa > 0 ? 0x04 : 0) | (xa < nx - 1 ? 0x10 : 0) | (ya < ny - 1 ? 0x20 : 0);
+    mB[j] = 0x08 | (yb > 0 ? 0x02 : 0) | (xb > 0 ? 0x04 : 0) | (xb < nx - 1 ? 0x10 : 0) | (yb < ny - 1 ? 0x20 : 0);
+  }
+  auto r0_of = [&](int z) { return (int64_t)z * P + off0; };
+  // a step is interior when the window of its plane is loadable (its rows then all exist)
+  auto interior = [&](int z) { const int64_t r0 = r0_of(z); return z >= 0 && z < nz && r0 - 256 >= 0 && r0 + TILE + 256 <= n; };
+
+  auto edge = [&](int z) {   // the clamped path of k_spmv_stencil2 on the rows of this tile in plane z (masks from memory)
+#pragma unroll
+    for (int j = 0; j < PPL; ++j) {
+      const int64_t r = r0_of(z) + (int64_t)j * 2 * TW + 2 * (int64_t)threadIdx.x;
+      if (!lane_in[j] || r >= n) continue;
+      const bool two = r + 1 < n;
+      const uint32_t m = mask2[r >> 1];
+      const uint32_t m0 = m & 0xffu, m1 = m >> 8;
+      const int64_t cmax = n - 2;
+      double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+      for (int k = 0; k < NSLOT; ++k) {
+        const int64_t c = r + d.delta[k];
+        int64_t lo = c < 0 ? 0 : (c > cmax ? cmax : c);
+        if (cmax < 0) lo = 0;
+        const int sh = (int)(c - lo);
+        double xa, xb;
+        if (n >= 2) ld_pair_u(x + lo, xa, xb);
+        else { xa = x[0]; xb = x[0]; }
+        const double v0 = sh == 1 ? xb : xa, v1 = sh == -1 ? xa : xb;
+        const double p0 = mul_nc(d.val[k], v0), p1 = mul_nc(d.val[k], v1);
+        s0 = ((m0 >> k) & 1u) ? add_(s0, p0) : s0;
+        s1 = ((m1 >> k) & 1u) ? add_(s1, p1) : s1;
+      }
+      if (shifted) {
+        double x0, x1;
+        if (two) ld_pair_u(x + r, x0, x1);
+        else { x0 = x[r]; x1 = x0; }
+        s0 = scl(sub_s(s0, mul_(theta, x0)), sigma);
+        s1 = scl(sub_s(s1, mul_(theta, x1)), sigma);
+      }
+      if (two) {
+        if (plain_st) st_pack(y + r, make_double2(s0, s1));
+        else st_pack_nt(y + r, make_double2(s0, s1));
+      } else {
+        if (plain_st) y[r] = s0;
+        else st_elem_nt(y + r, s0);
+      }
+    }
+  };
+  int zi0 = za, zi1 = zb;
+  while (zi0 < zi1 && !interior(zi0)) ++zi0;
+  while (zi1 > zi0 && !interior(zi1 - 1)) --zi1;
+  if (zi0 > za || zi1 < zb) {
+    for (int z = za; z < zb; ++z)
+      if (z < zi0 || z >= zi1) edge(z);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  if (zi0 >= zi1) return;   // (uniform over the workgroup: the barriers below match)
+
+  // window of plane zz (interior: inside [0, n)) into buffer `buf`: pieces of 128 rows, wave w copies pieces w, w + kWaves, ...
+  auto issue_w = [&](int zz, int buf) {
+    const double* bw = x + (r0_of(zz) - 256 + (int64_t)wave * 128);
+    uint32_t ldst = win0 + (uint32_t)buf * (uint32_t)kWinB + (uint32_t)wave * 1024u;
+    asm volatile("" : "+s"(bw));
+    asm volatile("" : "+s"(ldst));
+    asm volatile("s_nop 4" ::: "memory");
+#pragma unroll
+    for (int i = 0; i < kRounds; ++i)
+      if (wave + i * kWaves < kPieces) march_glds16(lane_w + (uint32_t)(i * kWaves) * 1024u, bw, ldst + (uint32_t)(i * kWaves) * 1024u);
+  };
+  f64x2m prev[PPL];   // the own pair of the plane below (x[r - P], x[r + 1 - P])
+  f64x2m top[PPL];    // the own pair of the plane above the LAST step's (no step reads that plane's window)
+  f64x2m acc[PPL];    // slots -P ... +nx of the rows of the step before
+  {
+    // (both inside [0, n): plane zi0 - 1 >= 0 ends below the end of window zi0; of plane zt, a whole plane, the lanes outside the
+    // plane read its first row of this tile instead)
+    const int zt = zi1 < nz ? zi1 : zi1 - 1;
+    const double* bp = x + (zi0 >= 1 ? r0_of(zi0 - 1) : r0_of(zi0));
+    const double* bt = x + r0_of(zt);
+    asm volatile("" : "+s"(bp));
+    asm volatile("" : "+s"(bt));
+    asm volatile("s_nop 4" ::: "memory");
+#pragma unroll
+    for (int j = 0; j < PPL; ++j) march_ld16(prev[j], lane_b[j], bp);
+#pragma unroll
+    for (int j = 0; j < PPL; ++j) march_ld16(top[j], lane_in[j] ? lane_b[j] : 0u, bt);
+  }
+  issue_w(zi0, 0);
+  if (zi0 + 1 < zi1) issue_w(zi0 + 1, 1);
+  // the rows of plane zrow: last slot (x[r + P] = nxt, present iff fpm), shift epilogue with their own pair (prev), store
+  auto finish = [&](int zrow, int j, f64x2m nxt, int fpm) {
+    double s0 = add_(acc[j].x, and_mask(mul_nc(d.val[KFP], nxt.x), fpm));
+    double s1 = add_(acc[j].y, and_mask(mul_nc(d.val[KFP], nxt.y), fpm));
+    if (shifted) {
+      s0 = scl(sub_s(s0, mul_(theta, prev[j].x)), sigma);
+      s1 = scl(sub_s(s1, mul_(theta, prev[j].y)), sigma);
+    }
+    f64x2m o2;
+    o2.x = s0;
+    o2.y = s1;
+    double* by = y + r0_of(zrow);
+    asm volatile("" : "+s"(by));
+    if (wave_has[j]) {   // (uniform: a wave with no lane in the plane issues nothing, nst counts the others)
+      if (lane_in[j]) march_st16(lane_b[j], o2, by, plain_st);
+    }
+  };
+  int bc = 0;   // buffer of plane z (plane z + i: (bc + i) % 3)
+  int i = 0;
+  for (int z = zi0; z < zi1; ++z, ++i) {
+    // landed: the window of plane z, issued two steps ago.  Behind it in this wave's queue, oldest first: [stores of plane z - 3]
+    // [window z + 1] [stores of plane z - 2] -- the first two steps of a range store nothing, the last issues no window
+    march_wait_vm((z + 1 < zi1 ? nw : 0) + nst * ((i >= 3 ? 1 : 0) + (i >= 2 ? 1 : 0)));
+    // (... and this wave's reads of the window of plane z - 1 have returned, whose buffer the copies below overwrite)
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    if (i == 0) {
+#pragma unroll
+      for (int j = 0; j < PPL; ++j) {
+        asm volatile("" : "+v"(prev[j]));
+        asm volatile("" : "+v"(top[j]));
+      }
+    }
+    if (z + 2 < zi1) issue_w(z + 2, bc == 0 ? 2 : bc - 1);
+    const int fm = z > 0 ? -1 : 0;
+#pragma unroll
+    for (int j = 0; j < PPL; ++j) {
+      const unsigned char* w = &win[0][0] + bc * kWinB + (256 * 8) + lane_b[j];
+      f64x2m v[NSLOT];
+#pragma unroll
+      for (int k = 0; k < NSLOT; ++k) {
+        if ((NEARM >> k) & 1u) {
+          const int off = (int)d.delta[k] * 8;
+          if (((ODDM >> k) & 1u) == 0) {
+            v[k] = *reinterpret_cast<const f64x2m*>(w + off);
+          } else {
+            typedef double f64x2u8 __attribute__((ext_vector_type(2), aligned(8)));
+            const f64x2u8 p = *reinterpret_cast<const f64x2u8*>(w + off);
+            v[k].x = p.x;
+            v[k].y = p.y;
+          }
+        }
+      }
+      v[KFM] = prev[j];
+      if (i > 0) finish(z - 1, j, v[KOWN], -1);   // (z - 1 < nz - 1: the rows below a plane that exists have their +P entry)
+      double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+      for (int k = 0; k < KFP; ++k) {
+        const double p0 = mul_nc(d.val[k], v[k].x), p1 = mul_nc(d.val[k], v[k].y);
+        s0 = add_(s0, and_mask(p0, k == KFM ? fm : __builtin_amdgcn_sbfe(mA[j], k, 1)));
+        s1 = add_(s1, and_mask(p1, k == KFM ? fm : __builtin_amdgcn_sbfe(mB[j], k, 1)));
+      }
+      acc[j].x = s0;
+      acc[j].y = s1;
+      prev[j] = v[KOWN];
+    }
+    bc = bc == 2 ? 0 : bc + 1;
+  }
+  // the rows of the last step: x[r + P] was loaded up front (no entry there when the range ends with the grid)
+#pragma unroll
+  for (int j = 0; j < PPL; ++j) finish(zi1 - 1, j, top[j], zi1 < nz ? -1 : 0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
 }  // namespace ksd
