@@ -354,44 +354,11 @@ template <class T> struct HipBackend : ks::Backend<T> {
     if (dbg) std::fprintf(stderr, "[deflate] j0 %d on %d dist %d ritz_valid %d nritz %d sstep_eff %d steps %d\n", j0, (int)ws->defl_on, (int)ws->ctx->distributed(), (int)ws->ritz_valid, (int)ws->ritz.size(), ws->sstep_eff, steps);
     if (!ws->defl_on || !ws->ritz_valid || ws->ritz.empty()) return 0;
     static const double ratio = [] { const char* e = std::getenv("KS_DEFLATE_RATIO"); const double v = e ? std::atof(e) : 1.5; return v > 1.0 ? v : 1.5; }();
+    // (the decision itself: ks_defl_plan.hpp, host only -- a leading block that is not quasi-triangular gives no plan)
     int nl = 0;
-    for (int j = 1; j <= j0 - 2; ++j)
-      if (H(j, j - 1) == T(0)) nl = j;
-    if (nl == 0) return 0;
-    using C = std::complex<double>;
-    std::vector<C> lam(nl);
-    std::vector<int> width(nl, 1);
-    for (int j = 0; j < nl;) {
-      if (j + 1 < nl && H(j + 1, j) != T(0)) {   // 2 x 2 block of the real Schur form
-        const C a = C(H(j, j)), b = C(H(j, j + 1)), c = C(H(j + 1, j)), d = C(H(j + 1, j + 1));
-        const C tr2 = 0.5 * (a + d), disc = std::sqrt(tr2 * tr2 - (a * d - b * c));
-        lam[j] = tr2 + disc; lam[j + 1] = tr2 - disc;
-        width[j] = 2; width[j + 1] = 0;
-        j += 2;
-      } else {
-        lam[j] = C(H(j, j));
-        ++j;
-      }
-    }
     double rest = 0.0;
-    for (auto z : ws->ritz) {
-      if (!std::isfinite(std::abs(z))) continue;
-      bool locked = false;
-      for (int j = 0; j < nl; ++j) locked = locked || std::abs(z - lam[j]) <= 1e-6 * std::max(1.0, std::abs(lam[j]));
-      if (!locked) rest = std::max(rest, std::abs(z));
-    }
-    if (dbg) std::fprintf(stderr, "[deflate] locked columns %d, largest other Ritz value %.3g, |lambda_0| %.3g\n", nl, rest, std::abs(lam[0]));
-    if (!(rest > 0.0)) return 0;
-    int nd = 0;
-    for (int j = 0; j < nl;) {
-      const int w = width[j] == 2 ? 2 : 1;
-      const double mag = w == 2 ? std::max(std::abs(lam[j]), std::abs(lam[j + 1])) : std::abs(lam[j]);
-      const double growth = std::pow(mag / rest, std::max(1, steps - 1));
-      if (!(mag > ratio * rest) || !(growth > 1e3) || nd + w > ksd::kDeflMax) break;
-      for (int q = 0; q < w; ++q) ex.push_back(lam[j + q]);
-      nd += w;
-      j += w;
-    }
+    const int nd = defl_plan_columns<T>(H.p, H.ld, j0, ws->ritz.data(), (int)ws->ritz.size(), ratio, steps, ksd::kDeflMax, ex, &nl, &rest);
+    if (dbg) std::fprintf(stderr, "[deflate] locked columns %d, largest other Ritz value %.3g, deflated %d, |lambda_0| %.3g\n", nl, rest, nd, nd > 0 ? std::abs(ex[0]) : 0.0);
     return nd;
   }
 

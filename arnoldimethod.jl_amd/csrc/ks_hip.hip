@@ -39,6 +39,7 @@ using ksd::kBlock;
 #include "ks_csr_layout.hpp" // host-only: which layout a stored matrix gets, and its host arrays
 #include "ks_halo_plan.hpp"  // host-only: what a distributed row block exchanges with its neighbours, and the peer-to-peer table
 #include "ks_stencil_geom.hpp" // host-only: are the masks of a stencil-mask layout the box rule of a grid
+#include "ks_defl_plan.hpp"    // host-only: which locked columns a Newton chain is deflated against
 #include "ks_halo.hpp"       // ... uploaded: ghost vector, transport buffers, the exchange in front of a product
 #include "ks_operators.hpp"  // ks_operator and its layouts
 #include "ks_sptrsv.hpp"     // shift-invert operator from triangular factors (sparse triangular solves)

@@ -360,7 +360,8 @@ def expand_steps(A, st, frm, to, stats):
 
 
 def defl_plan(H, j0, ritz, ratio=1.5, nmax=16, steps=10, tol=1.5e-8):
-    """HipBackend::defl_plan (csrc/ks_backend.hpp): the leading locked columns (decoupled leading block of H: src/run.jl:330 zeroes
+    """HipBackend::defl_plan (csrc/ks_defl_plan.hpp: defl_plan_columns; tests/test_defl_plan_cpu.py holds the two together case by
+    case): the leading locked columns (decoupled leading block of H: src/run.jl:330 zeroes
     the sub-diagonal entry behind it) whose eigenvalue exceeds `ratio` x the largest Ritz value of the rest.  Returns (number of
     columns, their eigenvalues)."""
     nl = 0
@@ -369,6 +370,12 @@ def defl_plan(H, j0, ritz, ratio=1.5, nmax=16, steps=10, tol=1.5e-8):
             nl = j
     if nl == 0 or ritz is None:
         return 0, []
+    # the leading block must be QUASI-TRIANGULAR (what a restart leaves of locked columns): two consecutive non-zero sub-diagonal
+    # entries above the boundary mean a general Hessenberg block (a caller's own H, an accidental zero in the active part) whose
+    # 1 x 1 / 2 x 2 diagonal blocks say nothing about its eigenvalues -- no plan
+    for j in range(1, nl - 1):
+        if H[j, j - 1] != 0 and H[j + 1, j] != 0:
+            return 0, []
     lam, width, j = [None] * nl, [1] * nl, 0
     while j < nl:
         if j + 1 < nl and H[j + 1, j] != 0:
@@ -457,12 +464,15 @@ def solve(A, v1, nev, which, tol, mindim, maxdim, restarts, dtype, s=4, **kw):
     active, k, prods = 0, mindim, mindim
     ritz = None
     check = kw.pop("check", True)
+    trace = kw.pop("trace", None)              # trace(cycle, k, st, stats) behind every expansion (tests/defl_cases.py)
     kw.setdefault("lock_tol", tol)             # (what the restart locks at: HipBackend::note_ritz hands it to defl_plan)
     expand(A, st, 1, mindim, stats, None, s, real)
     worst = dict(orth=0.0, rel=0.0)
-    for _ in range(restarts):
+    for cyc in range(restarts):
         expand(A, st, k + 1, maxdim, stats, ritz, s, real, **kw)
         prods += maxdim - k
+        if trace is not None:
+            trace(cyc, k, st, dict(stats))
         if check:
             V = st.true_basis(maxdim + 1)
             worst["orth"] = max(worst["orth"], float(np.linalg.norm(V.conj().T @ V - np.eye(maxdim + 1))))
