@@ -57,6 +57,11 @@ class ks_history(C.Structure):
     ]
 
 
+class ks_cheb_step(C.Structure):
+    """One Clenshaw step of a Chebyshev filter (ks_host_chebyshev_plan): slots -1 = x0 / y, -2 = none, 0..2 = temporaries."""
+    _fields_ = [("in_", C.c_int32), ("out", C.c_int32), ("w", C.c_int32), ("reserved", C.c_int32), ("sigma", C.c_double), ("gamma", C.c_double)]
+
+
 class ks_expand_stats(C.Structure):
     _fields_ = [("steps", C.c_int32), ("reorth", C.c_int32), ("breakdowns", C.c_int32), ("explicit_steps", C.c_int32)]
 
@@ -95,6 +100,8 @@ PROTOTYPES = {
     "ks_operator_tridiag_info": [vp, P(C.c_int), vp, P(i64), P(dbl), P(dbl)],
     "ks_operator_tridiag_pencil": [vp, i64, i32, vp, vp, vp, vp, vp, vp, i32, P(vp)],
     "ks_operator_product": [vp, i32, P(vp), P(vp)],
+    "ks_operator_chebyshev": [vp, vp, i32, dbl, dbl, vp, P(vp)],
+    "ks_operator_chebyshev_info": [vp, P(C.c_int), P(C.c_int), P(C.c_int64), P(C.c_int64)],
     "ks_operator_grid": [vp, i32, vp, i32, vp, vp, P(vp)],
     "ks_operator_grid_periodic": [vp, i32, vp, i32, vp, vp, vp, vp, P(vp)],
     "ks_operator_grid_star": [vp, i32, vp, i32, i32, vp, vp, P(vp)],
@@ -139,6 +146,8 @@ PROTOTYPES = {
     "ks_col_copy": [vp, i32, i32],
     "ks_apply": [vp, vp, i32, i32],
     "ks_debug_apply_shifted": [vp, vp, i32, i32, dbl, dbl, dbl, i32],
+    "ks_debug_apply_clenshaw": [vp, vp, i32, i32, i32, i32, dbl, dbl, dbl, dbl, i32],
+    "ks_host_chebyshev_plan": [i32, dbl, dbl, vp, vp, P(C.c_int)],
     "ks_gemv_t": [vp, i32, i32, vp],
     "ks_gemv_n_sub": [vp, i32, i32, vp],
     "ks_rotate": [vp, i32, i32, i32, vp, i32],

@@ -208,6 +208,15 @@ class Operator:
         check(_lib.load().ks_operator_format(self._h, C.byref(b), C.byref(d), C.byref(lay)))
         return dict(bytes_per_nnz=b.value, ndict=d.value, layout=_lib.LAYOUTS.get(lay.value, "?"))
 
+    @property
+    def chebyshev_info(self) -> dict:
+        """Degree and intermediate vectors of a `chebyshev_operator` (0 / 0 for any other operator), and the Clenshaw steps this
+        operator has run since its creation by the path they took: `fused_steps` in the product's own launch, `generic_steps` as
+        the product plus one streaming pass (`ks_operator_chebyshev_info`)."""
+        d, t, f, g = C.c_int(), C.c_int(), C.c_int64(), C.c_int64()
+        check(_lib.load().ks_operator_chebyshev_info(self._h, C.byref(d), C.byref(t), C.byref(f), C.byref(g)))
+        return dict(degree=d.value, temporaries=t.value, fused_steps=f.value, generic_steps=g.value)
+
     def close(self):
         # never touch a handle whose context is already gone (interpreter shutdown order is arbitrary)
         if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
@@ -472,6 +481,52 @@ def product_operator(*factors, ctx: Context | None = None) -> Operator:
     errs = [f.errors for f in factors if getattr(f, "errors", None) is not None]
     if errs:
         op.errors = _FactorErrors(errs)
+    return op
+
+
+def _chebyshev_args(degree, center, halfwidth, coeffs):
+    g = np.asarray(coeffs)
+    if g.ndim != 1 or g.dtype.kind not in "fiu":
+        raise ArgumentError(f"coeffs must be a 1-D sequence of real numbers (gamma_0 ... gamma_degree), got shape {g.shape}, dtype {g.dtype}")
+    g = np.ascontiguousarray(g, dtype=np.float64)
+    if degree is None:
+        degree = g.size - 1
+    elif g.size != int(degree) + 1:
+        raise DimensionMismatch(f"a filter of degree {degree} takes {int(degree) + 1} coefficients, got {g.size}")
+    return int(degree), float(center), float(halfwidth), g
+
+
+def host_chebyshev_plan(degree, center, halfwidth, coeffs):
+    """(steps, temporaries) of the Clenshaw schedule `chebyshev_operator` runs (`ks_host_chebyshev_plan`; no device needed): one
+    dict per operator step `out = sigma (A in - center in) - w + gamma x0` with the slots `in`, `out`, `w` (-1 = x0 as `in` / y as
+    `out`, -2 = none, 0..2 = the filter's intermediate vectors) and the scalars `sigma`, `gamma`."""
+    degree, center, halfwidth, g = _chebyshev_args(degree, center, halfwidth, coeffs)
+    steps = (_lib.ks_cheb_step * max(degree, 1))()
+    nt = C.c_int()
+    check(_lib.load().ks_host_chebyshev_plan(degree, center, halfwidth, g.ctypes.data, C.cast(steps, C.c_void_p), C.byref(nt)))
+    return [{"in": s.in_, "out": s.out, "w": s.w, "sigma": s.sigma, "gamma": s.gamma} for s in steps[:degree]], nt.value
+
+
+def chebyshev_operator(A: Operator, center, halfwidth, coeffs, ctx: Context | None = None) -> Operator:
+    """y = p(A) x with p(A) = sum_k coeffs[k] T_k((A - center) / halfwidth), every vector resident in HBM (`ks_operator_chebyshev`):
+    the spectral transformation for operators that cannot be factored.  `partialschur(F, which="LR")` finds the eigenvalues of A
+    that p maps highest -- `extras.chebyshev_window` / `extras.chebyshev_damping` make (center, halfwidth, coeffs) for an interior
+    window or a clustered low end; [center - halfwidth, center + halfwidth] must contain A's spectrum
+    (`extras.grid_spectrum_bounds`).  degree = len(coeffs) - 1 products per application; the grid operators can fuse each Clenshaw
+    step into their product (the default where that measured faster; KS_CHEB_FUSED=1 / 0 forces), every other operator adds one
+    streaming pass per step (`.chebyshev_info` counts both).  The filter
+    keeps A alive (`.base`); closing it leaves A usable.  An exception raised inside a Python callback A surfaces as that
+    exception from the call that applied the filter."""
+    if not isinstance(A, Operator):
+        raise ArgumentError(f"chebyshev_operator takes an Operator (as_operator(A) makes one), got {type(A).__name__}")
+    ctx = ctx or A.ctx
+    degree, center, halfwidth, g = _chebyshev_args(None, center, halfwidth, coeffs)
+    h = C.c_void_p()
+    check(_lib.load().ks_operator_chebyshev(ctx._h, A._h, degree, center, halfwidth, g.ctypes.data, C.byref(h)))
+    op = Operator(ctx, h, A.shape, A.dtype, keep=(A,))
+    op.base = A
+    if getattr(A, "errors", None) is not None:
+        op.errors = A.errors
     return op
 
 
@@ -1073,6 +1128,14 @@ class ArnoldiWorkspace:
         """Column jdst = sigma (A column jsrc - theta column jsrc): one Newton step of the s-step expansion (diagnostics)."""
         theta = complex(theta)
         _check_op(_lib.load().ks_debug_apply_shifted(A._h, self._h, jsrc, jdst, theta.real, theta.imag, float(sigma), int(bool(cacheable))), A)
+
+    def apply_clenshaw(self, A: Operator, jsrc: int, jdst: int, jw: int | None, jx0: int | None, theta, sigma: float, gamma: float,
+                       cacheable: bool = False):
+        """Column jdst = sigma (A column jsrc - theta column jsrc) - column jw + gamma column jx0: one Clenshaw step of a
+        Chebyshev filter (diagnostics).  jw / jx0 = None: no such term."""
+        theta = complex(theta)
+        _check_op(_lib.load().ks_debug_apply_clenshaw(A._h, self._h, jsrc, jdst, -1 if jw is None else jw, -1 if jx0 is None else jx0,
+                                                      theta.real, theta.imag, float(sigma), float(gamma), int(bool(cacheable))), A)
 
     def gemv_t(self, j: int, jv: int) -> np.ndarray:
         h = np.empty(j, dtype=self.dtype)

@@ -23,7 +23,8 @@
 // a z-range reads beyond each end, 2 R / zc of x, which neighbouring workgroups of the same XCD bring into its L2.  RULE for the
 // z-ranges (grid::plan): at least kGridMinZ * R = 8 R planes each, so that the plane re-read stays at most 25 %.
 // Every kernel argument `shifted`: bit 0 -- y = sigma (A x - theta x), the Newton step of the s-step expansion (as k_spmv_stencil2
-// stores it), bit 1 -- cacheable instead of streaming stores.  diag == nullptr: no potential, the diagonal entry is the centre tap.
+// stores it), bit 1 -- cacheable instead of streaming stores, bit 4 -- the tail of a Clenshaw step (GridTail; the launches pick the
+// kernel's TAIL instantiation by it).  diag == nullptr: no potential, the diagonal entry is the centre tap.
 // st: a breakdown of the batch ends the kernel at once.
 // Shared by the three kernels, below: the geometry at the head of the arguments (GridGeom), the tiles (GridTile, GridLds), the
 // work-item decode (grid_item), the owned points and their neighbour flags (grid_owned, grid_neighbours), the diagonal load
@@ -186,18 +187,30 @@ template <class T> __device__ __forceinline__ T grid_ldd(const T* diag, const Gr
   return ok && z < g.nz ? ld_val(diag + ((int64_t)z * P + o), true) : zero_of(T{});
 }
 
-// the end of a row: the fused Newton step, then the store (cacheable or streaming) if the point lies inside the grid
-template <class T> struct GridStore {
+// the tail of a Clenshaw step (ks_operator::apply_clenshaw), the last argument of every grid kernel; read only by the
+// instantiations with TAIL, which the launches pick where bit 4 of `shifted` is set
+template <class T> struct GridTail {
+  const T* w = nullptr;    // null: no such term
+  const T* x0 = nullptr;   // null: no such term
+  double gamma = 0.0;
+};
+// the end of a row: the fused Newton step, then -- TAIL -- the tail of a Clenshaw step, y = (t - w) + gamma x0 with w and x0 read
+// at the row's own position, then the store (cacheable or streaming); tail and store if the point lies inside the grid.
+// TAIL is a template parameter of every kernel: as a runtime branch the two loads per point cost the plain product 12 to 28
+// vector registers and 19 of the 48 instantiations an occupancy step (DESIGN); without TAIL the kernels are the ones they were.
+template <class T, bool TAIL = false> struct GridStore {
   T* const y;
   const int64_t P;
   const int shifted;
   const T theta;
   const double sigma;
+  const GridTail<T> tail;
   const bool plain = (shifted & 2) != 0;
   // s: the row's sum, xc: its own point, at offset o of plane z
   __device__ __forceinline__ void operator()(int z, int64_t o, bool in, T s, const T& xc) const {
     if (shifted & 1) s = scl(sub_s(s, mul_(theta, xc)), sigma);
     if (in) {
+      if constexpr (TAIL) s = clenshaw_tail(s, tail.w, tail.x0, tail.gamma, (int64_t)z * P + o);
       T* dst = y + ((int64_t)z * P + o);
       if (plain) *dst = s;
       else st_elem_nt(dst, s);
@@ -211,10 +224,10 @@ template <class T> struct GridStore {
 // +x neighbour of gx = nx - 1 is no halo cell but the LDS slot of the OWNED point gx = nx, which then holds x[0] of the line
 // (ldk, loff; likewise gy = ny); such a point is still never stored, and no row without that neighbour reads it.  z: plane -1 is
 // plane nz - 1, plane nz is plane 0 (only the first and the last z-range meet them).
-template <class T, int TX, int TY, class G>
+template <class T, int TX, int TY, class G, bool TAIL = false>
 __global__ void __launch_bounds__(kBlock)
     k_grid(const G g, const T* __restrict__ x, const T* __restrict__ diag, T* __restrict__ y, const DevState* __restrict__ st,
-           int shifted, T theta, double sigma) {
+           int shifted, T theta, double sigma, const GridTail<T> tail) {
   if (st && st->breakdown >= 0) return;
   constexpr bool PER = !std::is_same<G, GridDev<T>>::value;
   using L = GridLds<TX, TY, 1>;
@@ -225,7 +238,7 @@ __global__ void __launch_bounds__(kBlock)
   const int za = it.za, zb = it.zb;
   const int64_t P = it.P;
   const int tid = (int)threadIdx.x;
-  const GridStore<T> store{y, P, shifted, theta, sigma};
+  const GridStore<T, TAIL> store{y, P, shifted, theta, sigma, tail};
 
   int64_t off[PPT];   // in-plane offset of the owned points
   int li[PPT];        // ... and their place in the LDS tile
@@ -364,10 +377,10 @@ template <int J, int N, class F> __device__ __forceinline__ void grid_star_steps
   }
 }
 
-template <class T, int TX, int TY, int R>
+template <class T, int TX, int TY, int R, bool TAIL = false>
 __global__ void __launch_bounds__(kBlock)
     k_grid_star(const GridStarDev<T, R> g, const T* __restrict__ x, const T* __restrict__ diag, T* __restrict__ y,
-                const DevState* __restrict__ st, int shifted, T theta, double sigma) {
+                const DevState* __restrict__ st, int shifted, T theta, double sigma, const GridTail<T> tail) {
   if (st && st->breakdown >= 0) return;
   using L = GridLds<TX, TY, R>;
   constexpr int PPT = L::PPT, HY = L::HY, LW = L::LW, NH = L::NH;
@@ -378,7 +391,7 @@ __global__ void __launch_bounds__(kBlock)
   const int za = it.za, zb = it.zb;
   const int64_t P = it.P;
   const int tid = (int)threadIdx.x;
-  const GridStore<T> store{y, P, shifted, theta, sigma};
+  const GridStore<T, TAIL> store{y, P, shifted, theta, sigma, tail};
 
   int64_t off[PPT];   // in-plane offset of the owned points
   int li[PPT];        // ... and their place in the LDS tile
@@ -543,10 +556,10 @@ __global__ void __launch_bounds__(kBlock)
 // register pair, read by compile-time lane number (grid_wrap_lane).
 // z: the plane index wraps in the plane load (uniform); the planes within R of either end of a periodic z add the wrapped z groups,
 // under a uniform test, from the register sets that hold those planes already.
-template <class T, int TX, int TY, int R>
+template <class T, int TX, int TY, int R, bool TAIL = false>
 __global__ void __launch_bounds__(kBlock)
     k_grid_star_per(const GridStarPerDev<T, R> g, const T* __restrict__ x, const T* __restrict__ diag, T* __restrict__ y,
-                    const DevState* __restrict__ st, int shifted, T theta, double sigma) {
+                    const DevState* __restrict__ st, int shifted, T theta, double sigma, const GridTail<T> tail) {
   if (st && st->breakdown >= 0) return;
   using L = GridLds<TX, TY, R>;
   constexpr int PPT = L::PPT, HY = L::HY, LW = L::LW, NH = L::NH;
@@ -558,7 +571,7 @@ __global__ void __launch_bounds__(kBlock)
   const int za = it.za, zb = it.zb;
   const int64_t P = it.P;
   const int tid = (int)threadIdx.x;
-  const GridStore<T> store{y, P, shifted, theta, sigma};
+  const GridStore<T, TAIL> store{y, P, shifted, theta, sigma, tail};
   const double wl = grid_wrap_lane<T, R>(tid & 63);   // the wrap values, a word per lane
   // coordinate c of an LDS cell along an axis of extent m: where it is loaded from (outside [0, m): not at all)
   auto img = [](int c, int m, int per) { return !per ? c : c < 0 ? c + m : c >= m && c < m + R ? c - m : c; };
@@ -1040,8 +1053,14 @@ template <class D> struct GridOpBase : ks_operator {
   int nitems = 0;      // workgroups of a launch
   bool wide = false;   // the one-row tile (ny == 1)
   double bytes = 0.0;  // algorithmic bytes of one product
+  // The Clenshaw step runs in the product's launch by default.  Only where that MEASURED faster than the product and a streaming
+  // pass (216^3, Float64, profiles/grid_operator.txt): the 7-point operator, open and periodic, and the radius-2 star and the box
+  // operator with open boundaries.  The kernels run near half the HBM rate and take the two tail streams at that rate, the streaming
+  // pass takes its five at three quarters of it: with the long rows of radius 3 and 4, a coefficient stream, or the wrapped links of
+  // a periodic star or box edge the fused step is the slower one.  KS_CHEB_FUSED=1 / 0 forces either path for every grid operator.
+  bool cheb_fused_default = false;
   ~GridOpBase() override { (void)hipFree(diag); }
-  virtual void launch(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma) = 0;
+  virtual void launch(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma, const ksd::GridTail<D>& tail) = 0;
 
   // ctx, sizes, element type and the launch shape (geometry into g)
   void init(ks_ctx* c, const std::string& who, const grid::Shape& s, int radius, bool var, ksd::GridGeom& g) {
@@ -1068,13 +1087,26 @@ template <class D> struct GridOpBase : ks_operator {
     }
     bytes = (double)n_local * sizeof(D) * (potential ? 3.0 : 2.0);
   }
-  void product(const void* x, void* y, const DevState* st, int shifted, D theta, double sigma) {
+  void product(const void* x, void* y, const DevState* st, int shifted, D theta, double sigma, const ksd::GridTail<D>& tail = ksd::GridTail<D>{}) {
     KS_REQUIRE(x != y, KS_ERR_ARGUMENT, "grid operator: the product needs distinct x and y");
-    ProfScope ps(ctx, KSP_SPMV, bytes);
-    launch(static_cast<const D*>(x), static_cast<D*>(y), st, shifted, theta, sigma);
+    ProfScope ps(ctx, KSP_SPMV, bytes + (double)n_local * sizeof(D) * ((tail.w ? 1.0 : 0.0) + (tail.x0 ? 1.0 : 0.0)));
+    launch(static_cast<const D*>(x), static_cast<D*>(y), st, shifted, theta, sigma, tail);
     KS_HIP(hipGetLastError());
   }
   void apply(const void* x, void* y, const DevState* st) override { product(x, y, st, 0, D{}, 1.0); }
+  // the Clenshaw step in the same launch: the Newton step and the two-vector tail in the kernels' shared epilogue (GridStore), 40
+  // instead of 64 bytes per row in Float64 with a potential (KS_CHEB_FUSED, read per call: 0 the product and a streaming pass, 1
+  // this launch, unset cheb_fused_default)
+  void apply_clenshaw(const void* x, void* y, double tre, double tim, double sigma, const void* w, double gamma, const void* x0, int64_t ld,
+                      const DevState* st) override {
+    const int env = env_int("KS_CHEB_FUSED", -1);
+    if (!(env >= 0 ? env != 0 : cheb_fused_default)) { ks_operator::apply_clenshaw(x, y, tre, tim, sigma, w, gamma, x0, ld, st); return; }
+    KS_REQUIRE(y != x && y != w && y != x0, KS_ERR_ARGUMENT, "Clenshaw step: y must be distinct from x, w and x0");
+    D theta;
+    if constexpr (sizeof(D) == 8) theta = tre; else theta = D{tre, tim};
+    product(x, y, st, 1 | (shift_store_cacheable ? 2 : 0) | 16, theta, sigma, ksd::GridTail<D>{static_cast<const D*>(w), static_cast<const D*>(x0), gamma});
+    ++this->clenshaw_fused;
+  }
   // the Newton step in the same launch (KS_SHIFT_FUSED=0: the product and a streaming pass, like the stored layouts)
   void apply_shifted(const void* x, void* y, double tre, double tim, double sigma, int64_t ld, const DevState* st) override {
     if (!env_int("KS_SHIFT_FUSED", 1)) { ks_operator::apply_shifted(x, y, tre, tim, sigma, ld, st); return; }
@@ -1093,19 +1125,24 @@ template <class D> struct GridOp : GridOpBase<D> {
   int radius = 1;      // > 1: the star stencil, k_grid_star with the taps of `star` (k_grid_star_per where some axis wraps)
   D star[25] = {};     // its 6 radius + 1 slots
   D starw[24] = {};    // ... and the wrap values of its 6 radius links
-  void launch(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma) override {
+  // (bit 4 of `shifted`: the kernel instantiation with the tail of a Clenshaw step)
+  void launch(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma, const ksd::GridTail<D>& tail) override {
+    if (shifted & 16) launch_t<true>(x, y, st, shifted, theta, sigma, tail);
+    else launch_t<false>(x, y, st, shifted, theta, sigma, tail);
+  }
+  template <bool TAIL> void launch_t(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma, const ksd::GridTail<D>& tail) {
     using TL = ksd::GridTileOf<D>;
     const ksd::GridDev<D>& go = g;
-    if (radius == 2) launch_star<2>(x, y, st, shifted, theta, sigma);
-    else if (radius == 3) launch_star<3>(x, y, st, shifted, theta, sigma);
-    else if (radius == 4) launch_star<4>(x, y, st, shifted, theta, sigma);
+    if (radius == 2) launch_star<2, TAIL>(x, y, st, shifted, theta, sigma, tail);
+    else if (radius == 3) launch_star<3, TAIL>(x, y, st, shifted, theta, sigma, tail);
+    else if (radius == 4) launch_star<4, TAIL>(x, y, st, shifted, theta, sigma, tail);
     else if (periodic) {
-      if (wide) ksd::k_grid<D, TL::WX, 1, ksd::GridPerDev<D>><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma);
-      else ksd::k_grid<D, TL::TX, TL::TY, ksd::GridPerDev<D>><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma);
-    } else if (wide) ksd::k_grid<D, TL::WX, 1, ksd::GridDev<D>><<<nitems, kBlock, 0, ctx->stream>>>(go, x, diag, y, st, shifted, theta, sigma);
-    else ksd::k_grid<D, TL::TX, TL::TY, ksd::GridDev<D>><<<nitems, kBlock, 0, ctx->stream>>>(go, x, diag, y, st, shifted, theta, sigma);
+      if (wide) ksd::k_grid<D, TL::WX, 1, ksd::GridPerDev<D>, TAIL><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma, tail);
+      else ksd::k_grid<D, TL::TX, TL::TY, ksd::GridPerDev<D>, TAIL><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma, tail);
+    } else if (wide) ksd::k_grid<D, TL::WX, 1, ksd::GridDev<D>, TAIL><<<nitems, kBlock, 0, ctx->stream>>>(go, x, diag, y, st, shifted, theta, sigma, tail);
+    else ksd::k_grid<D, TL::TX, TL::TY, ksd::GridDev<D>, TAIL><<<nitems, kBlock, 0, ctx->stream>>>(go, x, diag, y, st, shifted, theta, sigma, tail);
   }
-  template <int R> void launch_star(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma) {
+  template <int R, bool TAIL> void launch_star(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma, const ksd::GridTail<D>& tail) {
     if (periodic) {
       using TP = ksd::GridTile<ksd::grid_star_per_half(sizeof(D), R)>;
       ksd::GridStarPerDev<D, R> gp;
@@ -1113,16 +1150,16 @@ template <class D> struct GridOp : GridOpBase<D> {
       for (int k = 0; k < 6 * R + 1; ++k) gp.tap[k] = star[k];
       for (int k = 0; k < 6 * R; ++k) gp.wrap[k] = starw[k];
       gp.px = g.px; gp.py = g.py; gp.pz = g.pz;
-      if (wide) ksd::k_grid_star_per<D, TP::WX, 1, R><<<nitems, kBlock, 0, ctx->stream>>>(gp, x, diag, y, st, shifted, theta, sigma);
-      else ksd::k_grid_star_per<D, TP::TX, TP::TY, R><<<nitems, kBlock, 0, ctx->stream>>>(gp, x, diag, y, st, shifted, theta, sigma);
+      if (wide) ksd::k_grid_star_per<D, TP::WX, 1, R, TAIL><<<nitems, kBlock, 0, ctx->stream>>>(gp, x, diag, y, st, shifted, theta, sigma, tail);
+      else ksd::k_grid_star_per<D, TP::TX, TP::TY, R, TAIL><<<nitems, kBlock, 0, ctx->stream>>>(gp, x, diag, y, st, shifted, theta, sigma, tail);
       return;
     }
     using TL = ksd::GridTileOf<D, R>;
     ksd::GridStarDev<D, R> gs;
     static_cast<ksd::GridGeom&>(gs) = g;
     for (int k = 0; k < 6 * R + 1; ++k) gs.tap[k] = star[k];
-    if (wide) ksd::k_grid_star<D, TL::WX, 1, R><<<nitems, kBlock, 0, ctx->stream>>>(gs, x, diag, y, st, shifted, theta, sigma);
-    else ksd::k_grid_star<D, TL::TX, TL::TY, R><<<nitems, kBlock, 0, ctx->stream>>>(gs, x, diag, y, st, shifted, theta, sigma);
+    if (wide) ksd::k_grid_star<D, TL::WX, 1, R, TAIL><<<nitems, kBlock, 0, ctx->stream>>>(gs, x, diag, y, st, shifted, theta, sigma, tail);
+    else ksd::k_grid_star<D, TL::TX, TL::TY, R, TAIL><<<nitems, kBlock, 0, ctx->stream>>>(gs, x, diag, y, st, shifted, theta, sigma, tail);
   }
 };
 
@@ -1154,6 +1191,7 @@ ks_operator* make_grid(ks_ctx* ctx, const std::string& who, int ndim, const int6
     if (op->periodic) half = ksd::grid_star_per_half(sizeof(D), radius);
   }
   op->radius = radius;
+  op->cheb_fused_default = radius == 1 || (radius == 2 && !op->periodic);
   op->init(ctx, who, s, radius, grid::tile_of(s, half), op->g);
   op->upload_diag(centre, potential);
   return op.release();

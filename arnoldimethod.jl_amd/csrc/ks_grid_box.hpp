@@ -62,10 +62,10 @@ __device__ __forceinline__ T grid_box_nine(T s, const T* __restrict__ tp, const 
   return s;
 }
 
-template <class T, int TX, int TY>
+template <class T, int TX, int TY, bool TAIL = false>
 __global__ void __launch_bounds__(kBlock)
     k_grid_box(const GridBoxDev<T> g, const T* __restrict__ x, const T* __restrict__ diag, T* __restrict__ y,
-               const DevState* __restrict__ st, int shifted, T theta, double sigma) {
+               const DevState* __restrict__ st, int shifted, T theta, double sigma, const GridTail<T> tail) {
   if (st && st->breakdown >= 0) return;
   using L = GridLds<TX, TY, 1>;
   constexpr int PPT = L::PPT, HY = L::HY, LW = L::LW;
@@ -76,7 +76,7 @@ __global__ void __launch_bounds__(kBlock)
   const int za = it.za, zb = it.zb;
   const int64_t P = it.P;
   const int tid = (int)threadIdx.x;
-  const GridStore<T> store{y, P, shifted, theta, sigma};
+  const GridStore<T, TAIL> store{y, P, shifted, theta, sigma, tail};
 
   int64_t off[PPT];   // in-plane offset of the owned points
   int li[PPT];        // ... and their place in the LDS tile
@@ -245,10 +245,10 @@ __device__ __forceinline__ T grid_box_nine_per(T s, const T* le, const T (&w)[9]
   return s;
 }
 
-template <class T, int TX, int TY>
+template <class T, int TX, int TY, bool TAIL = false>
 __global__ void __launch_bounds__(kBlock)
     k_grid_box_per(const GridBoxPerDev<T> g, const T* __restrict__ x, const T* __restrict__ diag, T* __restrict__ y,
-                   const DevState* __restrict__ st, int shifted, T theta, double sigma) {
+                   const DevState* __restrict__ st, int shifted, T theta, double sigma, const GridTail<T> tail) {
   if (st && st->breakdown >= 0) return;
   using L = GridLds<TX, TY, 1>;
   constexpr int PPT = L::PPT, HY = L::HY, LW = L::LW;
@@ -260,7 +260,7 @@ __global__ void __launch_bounds__(kBlock)
   const int za = it.za, zb = it.zb;
   const int64_t P = it.P;
   const int tid = (int)threadIdx.x;
-  const GridStore<T> store{y, P, shifted, theta, sigma};
+  const GridStore<T, TAIL> store{y, P, shifted, theta, sigma, tail};
   if (tid < 125) lt[tid] = g.link[tid];   // (first read after the first barrier of the z-loop)
 
   // a coordinate as it is LOADED: inside the grid itself, one step outside a periodic axis the other end, else -1
@@ -582,12 +582,18 @@ void host_box_matrix_periodic_entry(const std::string& who, int ndim, const int6
 }  // namespace grid
 
 template <class D> struct BoxGridOp : GridOpBase<D> {
+  BoxGridOp() { this->cheb_fused_default = true; }   // (measured: GridOpBase)
   using GridOpBase<D>::ctx; using GridOpBase<D>::diag; using GridOpBase<D>::nitems; using GridOpBase<D>::wide;
   ksd::GridBoxDev<D> g{};
-  void launch(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma) override {
+  // (bit 4 of `shifted`: the kernel instantiation with the tail of a Clenshaw step)
+  void launch(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma, const ksd::GridTail<D>& tail) override {
+    if (shifted & 16) launch_t<true>(x, y, st, shifted, theta, sigma, tail);
+    else launch_t<false>(x, y, st, shifted, theta, sigma, tail);
+  }
+  template <bool TAIL> void launch_t(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma, const ksd::GridTail<D>& tail) {
     using TL = ksd::GridTile<false>;
-    if (wide) ksd::k_grid_box<D, TL::WX, 1><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma);
-    else ksd::k_grid_box<D, TL::TX, TL::TY><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma);
+    if (wide) ksd::k_grid_box<D, TL::WX, 1, TAIL><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma, tail);
+    else ksd::k_grid_box<D, TL::TX, TL::TY, TAIL><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma, tail);
   }
 };
 
@@ -610,10 +616,15 @@ template <class D> struct BoxGridPerOp : GridOpBase<D> {
   ksd::GridBoxPerDev<D> g{};
   D* link = nullptr;
   ~BoxGridPerOp() override { (void)hipFree(link); }
-  void launch(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma) override {
+  // (bit 4 of `shifted`: the kernel instantiation with the tail of a Clenshaw step)
+  void launch(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma, const ksd::GridTail<D>& tail) override {
+    if (shifted & 16) launch_t<true>(x, y, st, shifted, theta, sigma, tail);
+    else launch_t<false>(x, y, st, shifted, theta, sigma, tail);
+  }
+  template <bool TAIL> void launch_t(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma, const ksd::GridTail<D>& tail) {
     using TL = ksd::GridTile<false>;
-    if (wide) ksd::k_grid_box_per<D, TL::WX, 1><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma);
-    else ksd::k_grid_box_per<D, TL::TX, TL::TY><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma);
+    if (wide) ksd::k_grid_box_per<D, TL::WX, 1, TAIL><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma, tail);
+    else ksd::k_grid_box_per<D, TL::TX, TL::TY, TAIL><<<nitems, kBlock, 0, ctx->stream>>>(g, x, diag, y, st, shifted, theta, sigma, tail);
   }
 };
 

@@ -50,10 +50,10 @@ __device__ __forceinline__ cd var_entry(cd h, double m) {
 // instantiated twice in the periodic form, with and without the two z-wrap links, and a uniform branch per plane picks one: only
 // plane 0 and plane nz - 1 have them, and with them in the one row every plane would keep x and c of plane z - 1 to the end of its
 // rows (DESIGN.md has the register counts of each form).
-template <class T, int TX, int TY, class G>
+template <class T, int TX, int TY, class G, bool TAIL = false>
 __global__ void __launch_bounds__(kBlock)
     k_grid_var(const G g, const T* __restrict__ x, const double* __restrict__ c, const T* __restrict__ diag,
-               T* __restrict__ y, const DevState* __restrict__ st, int shifted, T theta, double sigma) {
+               T* __restrict__ y, const DevState* __restrict__ st, int shifted, T theta, double sigma, const GridTail<T> tail) {
   if (st && st->breakdown >= 0) return;
   constexpr bool PER = !std::is_same<G, GridDev<T>>::value;
   using L = GridLds<TX, TY, 1>;
@@ -65,7 +65,7 @@ __global__ void __launch_bounds__(kBlock)
   const int za = it.za, zb = it.zb;
   const int64_t P = it.P;
   const int tid = (int)threadIdx.x;
-  const GridStore<T> store{y, P, shifted, theta, sigma};
+  const GridStore<T, TAIL> store{y, P, shifted, theta, sigma, tail};
 
   int64_t off[PPT];   // in-plane offset of the owned points
   int li[PPT];        // ... and their place in the LDS tiles
@@ -281,16 +281,21 @@ template <class D> struct VarGridOp : GridOpBase<D> {
   bool periodic = false;     // some axis wraps: the kernel's periodic instantiation
   double* coeff = nullptr;   // c[r], always Float64
   ~VarGridOp() override { (void)hipFree(coeff); }
-  void launch(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma) override {
+  // (bit 4 of `shifted`: the kernel instantiation with the tail of a Clenshaw step)
+  void launch(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma, const ksd::GridTail<D>& tail) override {
+    if (shifted & 16) launch_t<true>(x, y, st, shifted, theta, sigma, tail);
+    else launch_t<false>(x, y, st, shifted, theta, sigma, tail);
+  }
+  template <bool TAIL> void launch_t(const D* x, D* y, const DevState* st, int shifted, D theta, double sigma, const ksd::GridTail<D>& tail) {
     using TL = ksd::GridTileOf<D, 1, true>;
     using GP = ksd::GridPerDev<D>;
     using GO = ksd::GridDev<D>;
     const GO& go = g;
     if (periodic) {
-      if (wide) ksd::k_grid_var<D, TL::WX, 1, GP><<<nitems, kBlock, 0, ctx->stream>>>(g, x, coeff, diag, y, st, shifted, theta, sigma);
-      else ksd::k_grid_var<D, TL::TX, TL::TY, GP><<<nitems, kBlock, 0, ctx->stream>>>(g, x, coeff, diag, y, st, shifted, theta, sigma);
-    } else if (wide) ksd::k_grid_var<D, TL::WX, 1, GO><<<nitems, kBlock, 0, ctx->stream>>>(go, x, coeff, diag, y, st, shifted, theta, sigma);
-    else ksd::k_grid_var<D, TL::TX, TL::TY, GO><<<nitems, kBlock, 0, ctx->stream>>>(go, x, coeff, diag, y, st, shifted, theta, sigma);
+      if (wide) ksd::k_grid_var<D, TL::WX, 1, GP, TAIL><<<nitems, kBlock, 0, ctx->stream>>>(g, x, coeff, diag, y, st, shifted, theta, sigma, tail);
+      else ksd::k_grid_var<D, TL::TX, TL::TY, GP, TAIL><<<nitems, kBlock, 0, ctx->stream>>>(g, x, coeff, diag, y, st, shifted, theta, sigma, tail);
+    } else if (wide) ksd::k_grid_var<D, TL::WX, 1, GO, TAIL><<<nitems, kBlock, 0, ctx->stream>>>(go, x, coeff, diag, y, st, shifted, theta, sigma, tail);
+    else ksd::k_grid_var<D, TL::TX, TL::TY, GO, TAIL><<<nitems, kBlock, 0, ctx->stream>>>(go, x, coeff, diag, y, st, shifted, theta, sigma, tail);
   }
 };
 

@@ -40,11 +40,13 @@ using ksd::kBlock;
 #include "ks_halo_plan.hpp"  // host-only: what a distributed row block exchanges with its neighbours, and the peer-to-peer table
 #include "ks_stencil_geom.hpp" // host-only: are the masks of a stencil-mask layout the box rule of a grid
 #include "ks_defl_plan.hpp"    // host-only: which locked columns a Newton chain is deflated against
+#include "ks_cheb_plan.hpp"    // host-only: the Clenshaw schedule of a Chebyshev filter
 #include "ks_halo.hpp"       // ... uploaded: ghost vector, transport buffers, the exchange in front of a product
 #include "ks_operators.hpp"  // ks_operator and its layouts
 #include "ks_sptrsv.hpp"     // shift-invert operator from triangular factors (sparse triangular solves)
 #include "ks_tridiag.hpp"    // tridiagonal shift-invert operator: factored once on the host (ks_tridiag_plan.hpp), applied in HBM
 #include "ks_product.hpp"    // product of operators: generalized problems composed in HBM
+#include "ks_cheb.hpp"       // Chebyshev polynomial filter p(A): Clenshaw steps through the operator's apply_clenshaw
 #include "ks_grid.hpp"       // matrix-free grid operator: stencil taps in the kernel arguments plus a per-point diagonal
 #include "ks_grid_var.hpp"   // ... with a cell-centred coefficient: the link entries formed in registers from c
 #include "ks_grid_box.hpp"   // ... with the diagonal neighbours: the 9- / 27-point box stencil
@@ -414,6 +416,26 @@ int ks_operator_product(ks_ctx* ctx, int nops, ks_operator* const* ops, ks_opera
     KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, "ks_operator_product: single-GPU contexts only (the intermediate vectors are not sharded)");
     ctx->use();
     *out = make_product(ctx, nops, ops);
+  });
+}
+
+int ks_operator_chebyshev(ks_ctx* ctx, ks_operator* A, int degree, double center, double halfwidth, const double* coeffs, ks_operator** out) {
+  return guarded([&] {
+    KS_REQUIRE(ctx && out && A, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, "ks_operator_chebyshev: single-GPU contexts only (the intermediate vectors are not sharded)");
+    ctx->use();
+    *out = make_chebyshev(ctx, A, degree, center, halfwidth, coeffs);
+  });
+}
+
+int ks_operator_chebyshev_info(const ks_operator* op, int* degree, int* temporaries, int64_t* fused_steps, int64_t* generic_steps) {
+  return guarded([&] {
+    KS_REQUIRE(op, KS_ERR_ARGUMENT, "null operator");
+    const ChebOp* f = dynamic_cast<const ChebOp*>(op);
+    if (degree) *degree = f ? (int)f->plan.steps.size() : 0;
+    if (temporaries) *temporaries = f ? f->plan.temporaries : 0;
+    if (fused_steps) *fused_steps = op->clenshaw_fused;
+    if (generic_steps) *generic_steps = op->clenshaw_generic;
   });
 }
 
@@ -1088,6 +1110,39 @@ int ks_debug_apply_shifted(ks_operator* A, ks_workspace* ws, int jsrc, int jdst,
   });
 }
 
+// diagnostics: ONE Clenshaw step of a Chebyshev filter, V[:, jdst] = sigma (A V[:, jsrc] - theta V[:, jsrc]) - V[:, jw] + gamma V[:, jx0],
+// through the operator's apply_clenshaw -- the call ChebOp::apply (ks_cheb.hpp) makes per step.  jw / jx0 = -1: no such term.
+int ks_debug_apply_clenshaw(ks_operator* A, ks_workspace* ws, int jsrc, int jdst, int jw, int jx0, double theta_re, double theta_im,
+                            double sigma, double gamma, int cacheable_store) {
+  return guarded([&] {
+    KS_REQUIRE(A, KS_ERR_ARGUMENT, "null operator");
+    check_col(ws, jsrc);
+    check_col(ws, jdst);
+    if (jw != -1) check_col(ws, jw);
+    if (jx0 != -1) check_col(ws, jx0);
+    KS_REQUIRE(jsrc != jdst && jw != jdst && jx0 != jdst, KS_ERR_ARGUMENT, "the destination column must differ from the source, w and x0 columns");
+    KS_REQUIRE(A->n_local == ws->n && A->dtype == ws->dtype, KS_ERR_DIMENSION, "operator / workspace mismatch");
+    KS_REQUIRE(ws->dtype != KS_F64 || theta_im == 0.0, KS_ERR_ARGUMENT, "a Float64 product takes a real shift");
+    KS_REQUIRE(std::isfinite(gamma) && std::isfinite(sigma), KS_ERR_ARGUMENT, "sigma and gamma must be finite");
+    ws->ctx->use();
+    prov_drop(ws);  // the caller writes to V: the factorisation is no longer the library's own
+    materialize(ws);
+    reset_state(ws);  // (the kernels of a step look at the state: a breakdown left by an earlier batch would skip them)
+    A->in_scale = 1.0;
+    const bool saved = A->shift_store_cacheable;
+    A->shift_store_cacheable = cacheable_store != 0;
+    try {
+      A->apply_clenshaw(ws->col(jsrc), ws->col(jdst), theta_re, theta_im, sigma, jw == -1 ? nullptr : ws->col(jw), gamma,
+                        jx0 == -1 ? nullptr : ws->col(jx0), ws->ld, ws->st);
+      KS_HIP(hipStreamSynchronize(ws->ctx->stream));
+    } catch (...) {
+      A->shift_store_cacheable = saved;
+      throw;
+    }
+    A->shift_store_cacheable = saved;
+  });
+}
+
 int ks_gemv_t(ks_workspace* ws, int j, int jv, void* h_host) {
   return guarded([&] {
     check_col(ws, jv);
@@ -1640,6 +1695,18 @@ int ks_host_halo_plan(int64_t nrows_local, int64_t nghost, int64_t nnz, const in
       const P2pGhost g = p2p_ghost_size(P, (size_t)elem_size);
       p2p_ghost[0] = g.stride;
       p2p_ghost[1] = (int64_t)g.bytes;
+    }
+  });
+}
+
+int ks_host_chebyshev_plan(int degree, double center, double halfwidth, const double* coeffs, ks_cheb_step* steps, int* temporaries) {
+  return guarded([&] {
+    const ChebPlan P = chebyshev_plan(degree, center, halfwidth, coeffs);
+    if (temporaries) *temporaries = P.temporaries;
+    KS_REQUIRE(steps, KS_ERR_ARGUMENT, "ks_host_chebyshev_plan: null steps");
+    for (size_t i = 0; i < P.steps.size(); ++i) {
+      const ChebStep& s = P.steps[i];
+      steps[i] = ks_cheb_step{s.in, s.out, s.w, 0, s.sigma, s.gamma};
     }
   });
 }

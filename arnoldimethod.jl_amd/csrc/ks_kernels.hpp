@@ -1191,6 +1191,60 @@ __device__ __forceinline__ cd scl(cd a, double s) { return cd{a.x * s, a.y * s};
 __device__ __forceinline__ double from_real(double v, double) { return v; }
 __device__ __forceinline__ cd from_real(double v, cd) { return cd{v, 0.0}; }
 
+// ------------------------------------------------------------------------------------------------
+// One Clenshaw step of a Chebyshev series after a plain operator product (ks_operator::apply_clenshaw, operators without a fused
+// form):  y = ((sigma (y - theta x)) - w) + gamma x0  on rows < n, in ONE pass -- read y, x, w, x0, write y: 40 bytes per row in
+// Float64.  w == nullptr / x0 == nullptr drops that term (and its stream).  The tail of an element, shared with the grid kernels'
+// epilogue (GridStore, ks_grid.hpp): t is the Newton step, the two tail operations follow in this order.
+// Rows >= n are never written (the pad of a basis column or of a temporary stays zero).  16-byte accesses: every pointer is
+// 16-byte aligned (columns and temporaries start at multiples of 64 elements); the last row of an odd n in Float64 goes alone.
+// plain != 0: cacheable store (the next step's product gathers exactly this vector), else streaming.
+// ------------------------------------------------------------------------------------------------
+template <class T> __device__ __forceinline__ T clenshaw_tail(T t, const T* w, const T* x0, double gamma, int64_t i) {
+  if (w) t = sub_s(t, w[i]);
+  if (x0) t = add_(t, scl(x0[i], gamma));
+  return t;
+}
+template <class T>
+__global__ void __launch_bounds__(kBlock)
+    k_clenshaw_tail(T* __restrict__ y, const T* __restrict__ x, T theta, double sigma, const T* __restrict__ w, double gamma,
+                    const T* __restrict__ x0, int64_t n, int plain, const DevState* __restrict__ st) {
+  if (st && st->breakdown >= 0) return;
+  constexpr int R = Pack<T>::R;
+  int64_t pb, pe;
+  block_range(n / R, blockIdx.x, gridDim.x, pb, pe);
+  for (int64_t p = pb + threadIdx.x; p < pe; p += kBlock) {
+    const auto yv = ld_pack(y + p * R);
+    const auto xv = ld_pack(x + p * R);
+    if constexpr (sizeof(T) == 8) {
+      double2 t = make_double2(sigma * (yv.x - theta * xv.x), sigma * (yv.y - theta * xv.y));
+      if (w) {
+        const double2 wv = ld_pack(w + p * R);
+        t.x -= wv.x;
+        t.y -= wv.y;
+      }
+      if (x0) {
+        const double2 v = ld_pack(x0 + p * R);
+        t.x += gamma * v.x;
+        t.y += gamma * v.y;
+      }
+      if (plain) st_pack(y + p * R, t);
+      else st_pack_nt(y + p * R, t);
+    } else {
+      const cd tx = mul_(theta, xv);
+      const cd t = clenshaw_tail(cd{sigma * (yv.x - tx.x), sigma * (yv.y - tx.y)}, w, x0, gamma, p);
+      if (plain) st_pack(y + p, t);
+      else st_pack_nt(y + p, t);
+    }
+  }
+  if constexpr (R == 2) {
+    if ((n & 1) && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+      const int64_t i = n - 1;
+      y[i] = clenshaw_tail(sigma * (y[i] - theta * x[i]), w, x0, gamma, i);
+    }
+  }
+}
+
 template <class T, int NCW, int U, int WB, bool NT = true>
 __global__ void __launch_bounds__(kBlock)
     k_axpy_dots_cs(const T* __restrict__ V, int64_t ldv, int j, T* __restrict__ w, const T* __restrict__ coef,

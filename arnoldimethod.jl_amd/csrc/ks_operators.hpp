@@ -32,6 +32,13 @@ struct ks_operator {
   // y = sigma (A x - theta x): one step of the Newton basis of the s-step expansion (ks_block.hpp).  Default: the product
   // followed by a streaming pass (24 n bytes); layouts with a fused form override it.  theta = (re, im).
   virtual void apply_shifted(const void* x, void* y, double theta_re, double theta_im, double sigma, int64_t ld, const DevState* st);
+  // y = sigma (A x - theta x) - w + gamma x0, evaluated as ((t - w) + gamma x0) with t the Newton step: one Clenshaw step of a
+  // Chebyshev series (ks_cheb.hpp).  y is distinct from x, w and x0; a null w / x0 drops that term.  Default: the product followed
+  // by ONE streaming pass (k_clenshaw_tail: 40 n bytes in Float64); the grid operators do it in the product's own store.
+  // shift_store_cacheable picks the store, as for apply_shifted.  Every step an operator runs is counted by the path it took.
+  virtual void apply_clenshaw(const void* x, void* y, double theta_re, double theta_im, double sigma, const void* w, double gamma,
+                              const void* x0, int64_t ld, const DevState* st);
+  int64_t clenshaw_fused = 0, clenshaw_generic = 0;   // steps since creation: in the product's launch / product + streaming pass
 };
 
 namespace {
@@ -732,6 +739,28 @@ inline void ks_operator::apply_shifted(const void* x, void* y, double theta_re, 
     ksd::k_shift_scale<double><<<nbk, kBlock, 0, ctx->stream>>>(static_cast<double*>(y), static_cast<const double*>(x), theta_re, sigma, ld, st);
   } else {
     ksd::k_shift_scale<cd><<<nbk, kBlock, 0, ctx->stream>>>(static_cast<cd*>(y), static_cast<const cd*>(x), cd{theta_re, theta_im}, sigma, ld, st);
+  }
+  KS_HIP(hipGetLastError());
+}
+
+// default of ks_operator::apply_clenshaw: product + one streaming pass over rows < n_local (shift, scale and tail together)
+inline void ks_operator::apply_clenshaw(const void* x, void* y, double theta_re, double theta_im, double sigma, const void* w, double gamma,
+                                        const void* x0, int64_t, const DevState* st) {
+  KS_REQUIRE(y != x && y != w && y != x0, KS_ERR_ARGUMENT, "Clenshaw step: y must be distinct from x, w and x0");
+  auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+  KS_REQUIRE(aligned(x) && aligned(y) && aligned(w) && aligned(x0), KS_ERR_INTERNAL, "Clenshaw step: a vector is not 16-byte aligned");
+  apply(x, y, st);
+  ++clenshaw_generic;
+  if (n_local <= 0) return;
+  ProfScope ps(ctx, KSP_SCALE, (3.0 + (w ? 1.0 : 0.0) + (x0 ? 1.0 : 0.0)) * (double)n_local * (dtype == KS_F64 ? 8.0 : 16.0));
+  const int nbk = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)ctx->num_cu * 8, n_local / (2 * kBlock) + 1));
+  const int plain = shift_store_cacheable ? 1 : 0;
+  if (dtype == KS_F64) {
+    ksd::k_clenshaw_tail<double><<<nbk, kBlock, 0, ctx->stream>>>(static_cast<double*>(y), static_cast<const double*>(x), theta_re, sigma,
+                                                                  static_cast<const double*>(w), gamma, static_cast<const double*>(x0), n_local, plain, st);
+  } else {
+    ksd::k_clenshaw_tail<cd><<<nbk, kBlock, 0, ctx->stream>>>(static_cast<cd*>(y), static_cast<const cd*>(x), cd{theta_re, theta_im}, sigma,
+                                                              static_cast<const cd*>(w), gamma, static_cast<const cd*>(x0), n_local, plain, st);
   }
   KS_HIP(hipGetLastError());
 }

@@ -459,3 +459,122 @@ def q1_fem_taps(ndim, spacing=1.0):
     mass = outer(m1)
     stiff = sum(outer([k1[b] if b == a else m1[b] for b in range(ndim)]) for a in range(ndim))
     return np.ascontiguousarray(stiff).ravel(), np.ascontiguousarray(mass).ravel()
+
+
+# ------------------------------------------------------------------ Chebyshev polynomial filters (api.chebyshev_operator)
+def _cheb_interval(bounds):
+    try:
+        a, b = (float(v) for v in bounds)
+    except (TypeError, ValueError) as e:
+        raise api.ArgumentError(f"bounds must be a pair (a, b) that contains the spectrum, got {bounds!r}") from e
+    if not (np.isfinite(a) and np.isfinite(b) and a < b):
+        raise api.ArgumentError(f"bounds must be finite with a < b, got ({a}, {b})")
+    return a, b, 0.5 * (a + b), 0.5 * (b - a)
+
+
+def _cheb_degree(degree):
+    if isinstance(degree, (bool, np.bool_)) or not isinstance(degree, (int, np.integer)) or not 1 <= int(degree) <= 256:
+        raise api.ArgumentError(f"degree must be an integer in 1...256, got {degree!r}")
+    return int(degree)
+
+
+def jackson_factors(degree) -> np.ndarray:
+    """g_0 ... g_degree of the Jackson kernel for an expansion with degree + 1 terms: with N = degree + 1,
+    g_k = ((N - k + 1) cos(pi k / (N + 1)) + sin(pi k / (N + 1)) cot(pi / (N + 1))) / (N + 1).  The kernel is positive: the damped
+    expansion of a function with values in [0, 1] stays in [0, 1]."""
+    m = _cheb_degree(degree)
+    N = m + 1
+    k = np.arange(N, dtype=np.float64)
+    q = np.pi / (N + 1)
+    return ((N - k + 1) * np.cos(q * k) + np.sin(q * k) / np.tan(q)) / (N + 1)
+
+
+def chebyshev_window(lo, hi, bounds, degree, damping="jackson"):
+    """(center, halfwidth, coeffs) for `api.chebyshev_operator`: the Chebyshev expansion of the indicator of [lo, hi] on
+    bounds = (a, b), damped with the Jackson kernel (`damping="jackson"`; None: the truncated series, which overshoots).  With
+    c = (a + b) / 2, e = (b - a) / 2, t1 = acos((lo - c) / e), t2 = acos((hi - c) / e):
+        gamma_0 = (t1 - t2) / pi,   gamma_k = 2 (sin k t1 - sin k t2) / (k pi),
+    each multiplied by its Jackson factor.  The eigenvalues of A inside the window become the LARGEST of p(A): solve with
+    which="LR", then recover A's eigenvalues from the Schur vectors (README).  The filter is unbounded outside `bounds`: they must
+    contain A's spectrum (`grid_spectrum_bounds`)."""
+    a, b, c, e = _cheb_interval(bounds)
+    m = _cheb_degree(degree)
+    lo, hi = float(lo), float(hi)
+    if not a <= lo < hi <= b:
+        raise api.ArgumentError(f"the window must lie inside the bounds: need a <= lo < hi <= b, got [{lo}, {hi}] in [{a}, {b}]")
+    if damping not in ("jackson", None):
+        raise api.ArgumentError(f'damping must be "jackson" or None, got {damping!r}')
+    t1 = np.arccos(min(1.0, max(-1.0, (lo - c) / e)))
+    t2 = np.arccos(min(1.0, max(-1.0, (hi - c) / e)))
+    k = np.arange(1, m + 1, dtype=np.float64)
+    g = np.empty(m + 1)
+    g[0] = (t1 - t2) / np.pi
+    g[1:] = 2.0 * (np.sin(k * t1) - np.sin(k * t2)) / (k * np.pi)
+    if damping == "jackson":
+        g *= jackson_factors(m)
+    return c, e, g
+
+
+def _cheb_t(m, t):
+    """T_m(t) by the three-term recurrence in extended precision (no cancellation for |t| >= 1, where T_m grows)."""
+    t = np.longdouble(t)
+    p, q = np.longdouble(1.0), t
+    if m == 0:
+        return p
+    for _ in range(m - 1):
+        p, q = q, 2 * t * q - p
+    return q
+
+
+def chebyshev_damping(bounds, below, degree):
+    """(center, halfwidth, coeffs) for `api.chebyshev_operator`: p(t) = T_m((t - c) / e) / T_m((below - c) / e) on bounds = (a, b)
+    -- |p| <= 1 / |T_m((below - c) / e)| on [a, b], p(below) = 1, and p grows as fast as a polynomial of degree m can outside the
+    interval.  `below` lies at or beyond an end of `bounds`; only the top coefficient is non-zero.  With bounds = the part of the
+    spectrum to damp and `below` at the wanted end, the wanted eigenvalues are the largest of p(A) (which="LR"); bounds = the
+    whole spectrum and below = a separates a clustered low end: p rises to 1 towards a."""
+    a, b, c, e = _cheb_interval(bounds)
+    m = _cheb_degree(degree)
+    below = float(below)
+    if not np.isfinite(below) or a < below < b:
+        raise api.ArgumentError(f"`below` must be finite and lie at or beyond an end of the bounds, got {below} in ({a}, {b})")
+    top = _cheb_t(m, (np.longdouble(below) - np.longdouble(c)) / np.longdouble(e))
+    g = np.zeros(m + 1)
+    g[m] = float(np.longdouble(1.0) / top)
+    if not np.isfinite(g[m]) or g[m] == 0.0:
+        raise api.ArgumentError(f"T_{m} at `below` = {below} is out of range: lower the degree or move `below` closer to the bounds")
+    return c, e, g
+
+
+def chebyshev_eval(center, halfwidth, coeffs, t):
+    """p(t) = sum_k coeffs[k] T_k((t - center) / halfwidth) by Clenshaw's recurrence, elementwise: where the filter maps an
+    eigenvalue t of A."""
+    g = np.asarray(coeffs, dtype=np.float64)
+    s = (np.asarray(t, dtype=np.float64) - center) / halfwidth
+    b1 = np.zeros_like(s)
+    b2 = np.zeros_like(s)
+    for k in range(g.size - 1, 0, -1):
+        b1, b2 = g[k] + 2.0 * s * b1 - b2, b1
+    return g[0] + s * b1 - b2
+
+
+def grid_spectrum_bounds(taps, potential=None, radius=1):
+    """(a, b): the Gershgorin interval of a Hermitian constant-coefficient star operator (`api.grid_operator`,
+    `api.grid_star_operator`; 2 ndim radius + 1 taps with a real centre, a real potential): every eigenvalue lies in
+    [centre + min V - s, centre + max V + s] with s the sum of the moduli of the off-centre taps (a boundary row has fewer links,
+    its disc lies inside).  Safe bounds for `chebyshev_window` / `chebyshev_damping`; periodic axes with wrap values of the taps'
+    moduli (Bloch phases) have the same interval."""
+    t = np.asarray(taps)
+    if t.ndim != 1 or t.size % 2 != 1 or t.size < 3:
+        raise api.ArgumentError(f"taps must hold 2 ndim radius + 1 values, got shape {t.shape}")
+    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= 4 \
+            or (t.size - 1) % (2 * int(radius)) or not 1 <= (t.size - 1) // (2 * int(radius)) <= 3:
+        raise api.ArgumentError(f"{t.size} taps do not belong to a star stencil of radius {radius!r} in 1, 2 or 3 dimensions")
+    centre = t[t.size // 2]
+    v = np.zeros(1) if potential is None else np.asarray(potential).ravel()
+    if np.imag(centre) != 0 or np.any(np.imag(v) != 0):
+        raise api.ArgumentError("Gershgorin bounds on the real line need a Hermitian operator: the centre tap and the potential must be real")
+    if v.size == 0 or not (np.all(np.isfinite(v.real)) and np.all(np.isfinite(t))):
+        raise api.ArgumentError("taps and potential must be finite (and the potential non-empty)")
+    s = float(np.sum(np.abs(t)) - abs(centre))
+    d = float(np.real(centre))
+    return d + float(v.real.min()) - s, d + float(v.real.max()) + s

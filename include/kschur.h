@@ -411,6 +411,28 @@ int ks_operator_grid_box_periodic(ks_ctx* ctx, int ndim, const int64_t* dims /* 
                                   const void* taps /* 3^ndim values of dtype */, const void* potential /* n values of dtype, or NULL */,
                                   const int* periodic /* ndim flags, or NULL */, const void* links /* 5^ndim values of dtype, or NULL */,
                                   ks_operator** out);
+/* (xiii) Chebyshev polynomial filter:  y = p(A) x,  p(A) = sum_{k=0..degree} coeffs[k] T_k((A - center) / halfwidth) -- the spectral
+ * transformation for operators that cannot be factored (a 216^3 grid operator): run the eigensolver on p(A), whose LARGEST
+ * eigenvalues are the ones the coefficients select (an interior window, a clustered low end), and read A's eigenvalues off the
+ * Schur vectors (README).  Clenshaw's recurrence in `degree` operator steps
+ *     out = sigma (A in - center in) - w + gamma x          evaluated as ((t - w) + gamma x), t the Newton step of (viii),
+ * by the schedule ks_host_chebyshev_plan returns: `degree` products and, where A fuses the step into its product's store (the
+ * grid operators, (viii) - (xii-b): 40 instead of 64 bytes per row in Float64 with a potential), no other pass over the vectors;
+ * every other operator runs the product and ONE streaming pass per step.  The fused step is the default where it measured
+ * faster (the 7-point operator, and the radius-2 star and the box operator with open boundaries); KS_CHEB_FUSED=1 / 0 (read per step) forces
+ * the fused / the generic path for every grid operator.  A is BORROWED like a product's factors: the caller keeps it alive, destroying the filter
+ * leaves it usable.  Size, dtype and whether the filter can be enqueued ahead come from A; KS_F64 and KS_C64 operators are
+ * accepted, center, halfwidth and the coefficients are real.  1 <= degree <= 256, halfwidth > 0 and finite, center and every
+ * coefficient finite (KS_ERR_ARGUMENT otherwise, the message names the offending index); A made on `ctx`; single-GPU contexts
+ * only.  The filter owns min(degree - 1, 3) intermediate vectors; x is never written.  p is unbounded outside
+ * [center - halfwidth, center + halfwidth]: the interval must contain A's spectrum.  The Newton step of the s-step expansion on
+ * the filter is its product and a streaming pass. */
+int ks_operator_chebyshev(ks_ctx* ctx, ks_operator* A, int degree, double center, double halfwidth,
+                          const double* coeffs /* degree + 1 */, ks_operator** out);
+/* degree and intermediate vectors of a filter (0 / 0 for any other operator), and the Clenshaw steps `op` has run since its
+ * creation by the path they took: fused into the product's launch / product plus streaming pass.  A filter counts the steps of
+ * its own applications; any other operator the steps run on it (through a filter or through ks_debug_apply_clenshaw). */
+int ks_operator_chebyshev_info(const ks_operator* op, int* degree, int* temporaries, int64_t* fused_steps, int64_t* generic_steps);
 int ks_operator_destroy(ks_operator* op);
 int ks_operator_size(const ks_operator* op, int64_t* n_local, int64_t* nnz, int* dtype);
 /* Device layout chosen for a stored matrix at upload (mul!(y, A, x), src/expansion.jl:121; all layouts give bit-identical y):
@@ -609,6 +631,12 @@ int ks_apply(ks_operator* A, ks_workspace* ws, int jsrc, int jdst);
  * (what blocks of ten and more steps use), 0 the streaming one.  Drops the provenance of the factorisation like ks_apply. */
 int ks_debug_apply_shifted(ks_operator* A, ks_workspace* ws, int jsrc, int jdst, double theta_re, double theta_im, double sigma,
                            int cacheable_store);
+/* Diagnostics (tests/test_gpu_chebyshev.py): one Clenshaw step of a Chebyshev filter (xiii),
+ *     view(V,:,jdst+1) = sigma (A view(V,:,jsrc+1) - theta view(V,:,jsrc+1)) - view(V,:,jw+1) + gamma view(V,:,jx0+1),
+ * through the very call the filter makes per step.  jw = -1 / jx0 = -1: no such term; jdst differs from jsrc, jw and jx0.
+ * theta and cacheable_store as for ks_debug_apply_shifted.  Drops the provenance of the factorisation like ks_apply. */
+int ks_debug_apply_clenshaw(ks_operator* A, ks_workspace* ws, int jsrc, int jdst, int jw, int jx0, double theta_re, double theta_im,
+                            double sigma, double gamma, int cacheable_store);
 /* mul!(h, view(V,:,1:j)', view(V,:,jv+1))   src/expansion.jl:37,46,84,93   (h: j host values) */
 int ks_gemv_t(ks_workspace* ws, int j, int jv, void* h_host);
 /* mul!(view(V,:,jv+1), view(V,:,1:j), h, -1, 1)   src/expansion.jl:38,47,85,94 */
@@ -848,6 +876,21 @@ int ks_host_grid_box_matrix(int ndim, const int64_t* dims, int dtype, const void
 int ks_host_grid_box_matrix_periodic(int ndim, const int64_t* dims, int dtype, const void* taps, const void* potential,
                                      const int* periodic /* ndim flags, or NULL */, const void* links /* 5^ndim values, or NULL */,
                                      int64_t* rowptr /* n+1 */, int32_t* colidx, void* val, int64_t cap, int64_t* nnz);
+/* The schedule of ks_operator_chebyshev (xiii) without a device: Clenshaw's recurrence as `degree` steps
+ *     out = sigma (A in - center in) - w + gamma x0.
+ * With h = fl(2 / halfwidth), h1 = fl(1 / halfwidth), g = coeffs, m = degree:
+ *     m = 1:   (in x0, sigma fl(g[1] h1), no w, gamma g[0], out y);
+ *     step 1:  (in x0, sigma fl(g[m] h), no w, gamma g[m-1], out b_{m-1});
+ *     step 2 (k = m - 2):  (in b_{m-1}, sigma h (k = 0: h1), no w, gamma fl(g[m-2] - g[m]), out b_{m-2} (k = 0: y));
+ *     step s >= 3 (k = m - s):  (in b_{k+1}, sigma h (k = 0: h1), w b_{k+2}, gamma g[k], out b_k (k = 0: y)).
+ * Slots: -1 = x0 as `in`, y as `out`; -2 = none; 0 ... 2 = the filter's intermediate vectors, b_k in (m - 1 - k) mod 3, so out is
+ * never in, w or x0.  *temporaries = min(m - 1, 3).  Refusals as for the operator (KS_ERR_ARGUMENT). */
+typedef struct ks_cheb_step {
+  int32_t in, out, w, reserved;
+  double sigma, gamma;
+} ks_cheb_step;
+int ks_host_chebyshev_plan(int degree, double center, double halfwidth, const double* coeffs /* degree + 1 */,
+                           ks_cheb_step* steps /* degree */, int* temporaries);
 /* The plan, the factors and the HOST apply of ks_operator_tridiag_solve without a device (docs/src/index.md:234-259: the
  * factorize / ldiv! pair of the shift-invert recipe): x[:, k] = (T - sigma I)^-1 b[:, k] for nrhs columns (column k at b + k ldb,
  * x + k ldx; b and x distinct), walking exactly the arrays the device kernels read, in their order.  Same refusals as the operator. */

@@ -2,7 +2,7 @@
 """The matrix-free grid operator (ks_operator_grid) against the stored layouts, in the solver's own access pattern:
 
     python tools/grid_bench.py [--sizes 216,100] [--rounds 7] [--chains 5] [--cycles 20] [--no-solve] [--periodic] [--radius R] [--variable] [--box]
-                               [--complex [--wide]]
+                               [--complex [--wide]] [--chebyshev M]
 
 Float64, 7-point -Laplacian (+ a harmonic potential) on m x m x m grids.  Per size, in ONE process:
 
@@ -55,6 +55,10 @@ Float64, 7-point -Laplacian (+ a harmonic potential) on m x m x m grids.  Per si
              compared by.
   solve      iterations/s of nev = 20, mindim / maxdim = 20 / 40, :SR on (a) and (b): `cycles` timed restart cycles after 3 warm-up
              cycles (what bench.py times), alternating (a) and (b) -- and (e) and (f) with --periodic -- per round.
+
+  --chebyshev M   the Chebyshev filter (ks_operator_chebyshev) of degree M on the grid operator the other switches select: the
+             Clenshaw step fused into the product against product + streaming pass, cacheable against streaming intermediate stores,
+             and a filtered solve against the plain :SR solve (main_chebyshev).
 
 Prints one JSON line per size and a short table; fractions are of the 8 TB/s HBM rate."""
 import argparse
@@ -157,7 +161,13 @@ def main():
     ap.add_argument("--box", action="store_true", help="the 27-point box operator against its stored matrix and the 7-point floor")
     ap.add_argument("--complex", action="store_true", help="the selected grid operators alone, in ComplexF64: products only")
     ap.add_argument("--wide", action="store_true", help="with --complex: the m^2 x 1 x m grid (one-row tiles)")
+    ap.add_argument("--chebyshev", type=int, default=None, metavar="M", help="the Chebyshev filter of degree M on the selected grid operator: fused against generic steps, and a filtered solve")
     args = ap.parse_args()
+    if args.chebyshev is not None:
+        if args.complex:
+            raise SystemExit("--chebyshev takes no --complex")
+        main_chebyshev(args)
+        return
     if args.complex:
         main_complex(args)
         return
@@ -493,6 +503,153 @@ def main_complex(args):
         report(out, prod, m, n, args)
         for op in ops.values():
             op.close()
+
+
+CHEB_VARIANTS = {   # name -> environment of the run (read per step / per product by the library)
+    "fused": {"KS_CHEB_FUSED": "1"},                               # the step in the product's launch, intermediates cacheable
+    "generic": {"KS_CHEB_FUSED": "0"},                             # product + streaming pass
+    "fused_streaming": {"KS_CHEB_FUSED": "1", "KS_CHEB_PLAIN": "0"},   # ... with streaming stores for the intermediate steps
+    "generic_streaming": {"KS_CHEB_FUSED": "0", "KS_CHEB_PLAIN": "0"},
+}
+
+
+def _cheb_env(env):
+    for k in ("KS_CHEB_FUSED", "KS_CHEB_PLAIN"):
+        os.environ.pop(k, None)
+    os.environ.update(env)
+
+
+def _cheb_family(args, shape, V, ctx):
+    """(name, operator with the potential, safe spectrum bounds) of the family the switches select."""
+    from arnoldimethod_jl_amd import extras
+
+    if args.box:
+        taps = extras.tensor_laplacian_taps(TENSOR)
+        s = float(np.abs(taps).sum() - abs(taps[taps.size // 2]))
+        return "box", ks.grid_box_operator(shape, taps, V, ctx=ctx, periodic=args.periodic or None), (taps[taps.size // 2] + V.min() - s, taps[taps.size // 2] + V.max() + s)
+    if args.variable:
+        c = jump_coefficient(shape)
+        taps, diag = extras.diffusion_terms(shape, c, potential=V, periodic=True if args.periodic else None)
+        B = float(np.abs(diag).max() + 2.0 * c.max() * (np.abs(taps).sum() - abs(taps[3])))   # a crude Gershgorin radius: timing only
+        return "variable", ks.grid_variable_operator(shape, taps, c, diag, ctx=ctx, periodic=True if args.periodic else None), (-B, B)
+    R = 1 if args.radius is None else args.radius
+    taps = LAPLACE if R == 1 else extras.fd_laplacian_taps(3, 2 * R)
+    if args.periodic:
+        op = ks.grid_star_operator(shape, taps, R, V, ctx=ctx, periodic=True)
+    else:
+        op = ks.grid_operator(shape, taps, V, ctx=ctx, radius=R)
+    return ("7-point" if R == 1 else "star%d" % R), op, extras.grid_spectrum_bounds(taps, V, radius=R)
+
+
+def main_chebyshev(args):
+    """--chebyshev M: the Chebyshev filter of degree M (ks_operator_chebyshev) on the grid operator the other switches select
+    (--radius R, --variable, --box, each with --periodic; with the potential), per size in ONE process:
+
+      steps    the filter applied column i -> i + 1 over four columns, `chains` chains per round, the variants of CHEB_VARIANTS and
+               the plain product of the same operator alternating inside every round: host clock per STEP (one product and what
+               the variant adds), and in a pass of its own the HIP-event time of the kernels alone (classes spmv + scale);
+      solve    nev = 20, 20 / 40, tol = sqrt(eps), at most 200 restarts: the plain :SR solve of the operator against which = LR on
+               the damping polynomial of degree M that is 1 at the lower spectrum bound and damps everything above the wanted
+               eigenvalues (the cut is taken from the plain solve's own result), fused and generic: restarts, products of A,
+               seconds, converged pairs, and the residuals ||A x - theta x|| of the filtered solve's vectors (on the device)."""
+    from arnoldimethod_jl_amd import extras
+
+    M = args.chebyshev
+    ctx = ks.Context(0)
+    for m in (int(s) for s in args.sizes.split(",")):
+        shape, n = (m, m, m), m ** 3
+        V = ks.matrices.harmonic_potential(shape)
+        family, A, bounds = _cheb_family(args, shape, V, ctx)
+        a, b = bounds
+        F = ks.chebyshev_operator(A, *extras.chebyshev_window(a + 0.05 * (b - a), a + 0.10 * (b - a), bounds, M))
+        ws = ks.ArnoldiWorkspace(n, 4, np.float64, ctx=ctx)
+        names = list(CHEB_VARIANTS) + ["plain_product"]
+
+        def run(name):
+            _cheb_env(CHEB_VARIANTS.get(name, {}))
+            for _c in range(args.chains):
+                for i in range(4):
+                    ws.apply(A if name == "plain_product" else F, i, i + 1)
+            return args.chains * 4 * (1 if name == "plain_product" else M)
+
+        ws.fill_uniform(0, 1)
+        for name in names:
+            run(name)
+        ctx.synchronize()
+        us = {name: [] for name in names}
+        for _ in range(args.rounds):
+            for name in names:
+                ws.fill_uniform(0, 1)
+                ctx.synchronize()
+                t0 = time.perf_counter()
+                steps = run(name)
+                ctx.synchronize()
+                us[name].append(1e6 * (time.perf_counter() - t0) / steps)
+        ctx.profile_enable(True)
+        ev = {name: [] for name in names}
+        for _ in range(args.rounds):
+            for name in names:
+                ws.fill_uniform(0, 1)
+                ctx.synchronize()
+                ctx.profile_reset()
+                steps = run(name)
+                ctx.synchronize()
+                p = ctx.profile_get()
+                ev[name].append(1e3 * (p["spmv"]["ms"] + p["scale"]["ms"]) / steps)
+        ctx.profile_enable(False)
+        _cheb_env({})
+        elem = 8.0
+        by = {"fused": 5 * elem, "fused_streaming": 5 * elem, "generic": 8 * elem, "generic_streaming": 8 * elem, "plain_product": 3 * elem}
+        if args.variable:
+            by = {k: v + elem for k, v in by.items()}
+        out = dict(m=m, n=n, family=family, periodic=args.periodic, degree=M, chains=args.chains, steps_per_round=args.chains * 4 * M,
+                   info=F.chebyshev_info, us_per_step={k: stats(v) for k, v in us.items()}, event_us_per_step={k: stats(v) for k, v in ev.items()},
+                   bytes_per_row=by)
+        if not args.no_solve:
+            tol = float(np.sqrt(np.finfo(np.float64).eps))
+            v1 = ks.matrices.start_vector(n)
+            solves = {}
+            t0 = time.perf_counter()
+            dec, hist = ks.partialschur(A, v1=v1, nev=NEV, which="SR", tol=tol, mindim=MINDIM, maxdim=MAXDIM, ctx=ctx)
+            ctx.synchronize()
+            solves["plain_SR"] = dict(seconds=time.perf_counter() - t0, restarts=hist.restarts, products_of_A=hist.mvproducts, nconverged=hist.nconverged,
+                                      converged=hist.converged)
+            low = np.sort(dec.eigenvalues.real)
+            cut = low[-1] + 0.5 * (low[-1] - low[0]) if low.size > 1 else a + 0.05 * (b - a)
+            c, e, g = extras.chebyshev_damping((cut, b), below=a, degree=M)
+            Fd = ks.chebyshev_operator(A, c, e, g)
+            for name in ("fused", "generic"):
+                _cheb_env(CHEB_VARIANTS[name])
+                t0 = time.perf_counter()
+                dec_f, hist_f = ks.partialschur(Fd, v1=v1, nev=NEV, which="LR", tol=tol, mindim=MINDIM, maxdim=MAXDIM, ctx=ctx)
+                ctx.synchronize()
+                sec = time.perf_counter() - t0
+                rec = dict(seconds=sec, restarts=hist_f.restarts, products_of_A=hist_f.mvproducts * M, nconverged=hist_f.nconverged, converged=hist_f.converged, cut=float(cut))
+                if dec_f.nconverged:
+                    X = ks.schur_vectors(dec_f)
+                    theta = np.real(np.diag(ks.gram(X, X.apply(A))))
+                    r, _qn = ks.residuals(A, X, theta)
+                    rec.update(theta_min=float(theta.min()), theta_max=float(theta.max()), max_residual=float(r.max()),
+                               lowest_of_plain=float(low[0]) if low.size else None)
+                    X.close()
+                solves[name] = rec
+            _cheb_env({})
+            Fd.close()
+            out["solve"] = solves
+        print(json.dumps(out), flush=True)
+        print("m = %d (n = %d), %s%s, degree %d: us per Clenshaw step, mean +- std [min, max] over %d rounds of %d steps; B/row; fraction of 8 TB/s" % (
+            m, n, family, " periodic" if args.periodic else "", M, args.rounds, args.chains * 4 * M))
+        for name in names:
+            s, e_ = out["us_per_step"][name], out["event_us_per_step"][name]
+            print("  %-18s %8.2f +- %5.2f  [%7.2f, %7.2f]   %4.0f B/row  %5.1f %%   kernels alone (HIP events) %7.2f us  [%7.2f, %7.2f]  %5.1f %%" % (
+                name, s["mean"], s["std"], s["min"], s["max"], by[name], 100 * by[name] * n / (s["mean"] * 1e-6) / PEAK, e_["mean"], e_["min"], e_["max"],
+                100 * by[name] * n / (e_["mean"] * 1e-6) / PEAK))
+        for name, rec in out.get("solve", {}).items():
+            print("  solve %-10s %s" % (name, rec))
+        sys.stdout.flush()
+        ws.close()
+        F.close()
+        A.close()
 
 
 if __name__ == "__main__":
