@@ -217,6 +217,16 @@ class Operator:
         check(_lib.load().ks_operator_chebyshev_info(self._h, C.byref(d), C.byref(t), C.byref(f), C.byref(g)))
         return dict(degree=d.value, temporaries=t.value, fused_steps=f.value, generic_steps=g.value)
 
+    @property
+    def cg_info(self) -> dict:
+        """Counters of a `cg_operator` since its creation (`ks_operator_cg_info`; ArgumentError for any other operator): solves,
+        iterations of all of them, iterations and the recurrence's relative residual sqrt(rho' / rho0) of the last solve, and the
+        largest such residual of any solve."""
+        a, it, last = C.c_int64(), C.c_int64(), C.c_int()
+        rel, worst = C.c_double(), C.c_double()
+        check(_lib.load().ks_operator_cg_info(self._h, C.byref(a), C.byref(it), C.byref(last), C.byref(rel), C.byref(worst)))
+        return dict(applications=a.value, iterations=it.value, last_iterations=last.value, last_relres=rel.value, worst_relres=worst.value)
+
     def close(self):
         # never touch a handle whose context is already gone (interpreter shutdown order is arbitrary)
         if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
@@ -527,6 +537,40 @@ def chebyshev_operator(A: Operator, center, halfwidth, coeffs, ctx: Context | No
     op.base = A
     if getattr(A, "errors", None) is not None:
         op.errors = A.errors
+    return op
+
+
+def host_cg_step(rho, pq, rho_new, stop):
+    """(alpha, beta, done, fail) of one conjugate-gradient iteration as `cg_operator`'s kernels decide it (`ks_host_cg_step`; no
+    device needed): from rho = ||r||^2, pq = Re p^H (A - shift) p, rho_new = ||r - alpha q||^2 and stop = tol^2 ||b||^2.  `fail`
+    (pq not finite or <= 0, alpha or rho_new not finite) gives alpha = beta = 0; `done` is rho_new <= stop and gives beta = 0."""
+    a, b, d, f = C.c_double(), C.c_double(), C.c_int(), C.c_int()
+    check(_lib.load().ks_host_cg_step(float(rho), float(pq), float(rho_new), float(stop), C.byref(a), C.byref(b), C.byref(d), C.byref(f)))
+    return a.value, b.value, bool(d.value), bool(f.value)
+
+
+def cg_operator(A: Operator, shift=0.0, tol=1e-13, maxit=1000, check_every=0, ctx: Context | None = None) -> Operator:
+    """y ~ (A - shift I)^-1 x by conjugate gradients, every vector resident in HBM and every scalar of the recurrence on the device
+    (`ks_operator_cg`): the inner iterative solver for operators that have nothing to factor -- the mass matrix of matrix-free
+    finite elements (`extras.generalized_cg_operator`), any Hermitian operator with `shift` below its spectrum.  A - shift I must be
+    Hermitian positive definite (Float64 or ComplexF64; `shift` is real).  The solve stops when the recurrence's residual is below
+    `tol` ||x||; `maxit` bounds the iterations, the host looks at the device's record every `check_every` iterations (0: the
+    library default, 8) -- neither the result nor the iteration count depends on it, and equal inputs give equal bits.
+
+    The solve is linear in x only up to tol * cond(A - shift I), and the Arnoldi relation of an outer `partialschur` on this
+    operator inherits that: choose `tol` at least 100 times tighter than the outer tolerance.
+
+    Refused (ArgumentError): an A of another context, one that cannot be enqueued ahead (a host callback, another `cg_operator`, a
+    product or filter of one), a context of several ranks, tol outside (0, 1), maxit < 1, check_every < 0, a shift that is not
+    finite.  At apply time "not positive definite" and "did not converge" raise HipError; the operator stays usable.  `.cg_info`
+    counts solves and iterations.  The operator keeps A alive (`.base`); closing it leaves A usable."""
+    if not isinstance(A, Operator):
+        raise ArgumentError(f"cg_operator takes an Operator (as_operator(A) makes one), got {type(A).__name__}")
+    ctx = ctx or A.ctx
+    h = C.c_void_p()
+    check(_lib.load().ks_operator_cg(ctx._h, A._h, float(shift), float(tol), int(maxit), int(check_every), C.byref(h)))
+    op = Operator(ctx, h, A.shape, A.dtype, keep=(A,))
+    op.base = A
     return op
 
 

@@ -41,12 +41,14 @@ using ksd::kBlock;
 #include "ks_stencil_geom.hpp" // host-only: are the masks of a stencil-mask layout the box rule of a grid
 #include "ks_defl_plan.hpp"    // host-only: which locked columns a Newton chain is deflated against
 #include "ks_cheb_plan.hpp"    // host-only: the Clenshaw schedule of a Chebyshev filter
+#include "ks_cg_plan.hpp"      // host-only: the scalar step of the conjugate-gradient solve and its device record
 #include "ks_halo.hpp"       // ... uploaded: ghost vector, transport buffers, the exchange in front of a product
 #include "ks_operators.hpp"  // ks_operator and its layouts
 #include "ks_sptrsv.hpp"     // shift-invert operator from triangular factors (sparse triangular solves)
 #include "ks_tridiag.hpp"    // tridiagonal shift-invert operator: factored once on the host (ks_tridiag_plan.hpp), applied in HBM
 #include "ks_product.hpp"    // product of operators: generalized problems composed in HBM
 #include "ks_cheb.hpp"       // Chebyshev polynomial filter p(A): Clenshaw steps through the operator's apply_clenshaw
+#include "ks_cg.hpp"         // conjugate-gradient solve (A - theta)^-1: fused vector kernels, scalars and the stopping test on the device
 #include "ks_grid.hpp"       // matrix-free grid operator: stencil taps in the kernel arguments plus a per-point diagonal
 #include "ks_grid_var.hpp"   // ... with a cell-centred coefficient: the link entries formed in registers from c
 #include "ks_grid_box.hpp"   // ... with the diagonal neighbours: the 9- / 27-point box stencil
@@ -436,6 +438,29 @@ int ks_operator_chebyshev_info(const ks_operator* op, int* degree, int* temporar
     if (temporaries) *temporaries = f ? f->plan.temporaries : 0;
     if (fused_steps) *fused_steps = op->clenshaw_fused;
     if (generic_steps) *generic_steps = op->clenshaw_generic;
+  });
+}
+
+int ks_operator_cg(ks_ctx* ctx, ks_operator* A, double shift, double tol, int maxit, int check_every, ks_operator** out) {
+  return guarded([&] {
+    KS_REQUIRE(ctx && out && A, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, "ks_operator_cg: single-GPU contexts only (the reductions of the solve are not summed across ranks)");
+    ctx->use();
+    *out = make_cg(ctx, A, shift, tol, maxit, check_every);
+  });
+}
+
+int ks_operator_cg_info(const ks_operator* op, int64_t* applications, int64_t* iterations, int* last_iterations, double* last_relres,
+                        double* worst_relres) {
+  return guarded([&] {
+    KS_REQUIRE(op, KS_ERR_ARGUMENT, "null operator");
+    const CgOp* c = dynamic_cast<const CgOp*>(op);
+    KS_REQUIRE(c, KS_ERR_ARGUMENT, "ks_operator_cg_info: not an operator made by ks_operator_cg");
+    if (applications) *applications = c->applications;
+    if (iterations) *iterations = c->iterations;
+    if (last_iterations) *last_iterations = c->last_iterations;
+    if (last_relres) *last_relres = c->last_relres;
+    if (worst_relres) *worst_relres = c->worst_relres;
   });
 }
 
@@ -1708,6 +1733,16 @@ int ks_host_chebyshev_plan(int degree, double center, double halfwidth, const do
       const ChebStep& s = P.steps[i];
       steps[i] = ks_cheb_step{s.in, s.out, s.w, 0, s.sigma, s.gamma};
     }
+  });
+}
+
+int ks_host_cg_step(double rho, double pq, double rho_new, double stop, double* alpha, double* beta, int* done, int* fail) {
+  return guarded([&] {
+    const CgStep s = cg_step(rho, pq, rho_new, stop);
+    if (alpha) *alpha = s.alpha;
+    if (beta) *beta = s.beta;
+    if (done) *done = s.done;
+    if (fail) *fail = s.fail;
   });
 }
 

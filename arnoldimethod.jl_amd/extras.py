@@ -169,6 +169,20 @@ def generalized_shift_invert(A, B, sigma=0.0, ctx: api.Context | None = None, **
     return op
 
 
+def generalized_cg_operator(A: api.Operator, B: api.Operator, **cg) -> api.Operator:
+    """`api.Operator` for y = B^{-1} (A x) with A and B device operators and B Hermitian positive definite: the reference's recipe
+    for generalized problems A x = B x lambda (docs/src/index.md:273-287) where B has nothing to factor -- the consistent mass
+    matrix of matrix-free finite elements (`q1_fem_taps`).  `api.product_operator(api.cg_operator(B, **cg), A)`: the solve is
+    conjugate gradients on the device (keywords are passed on to `api.cg_operator`), the eigenvalues of the operator are the
+    pencil's, so `partialschur(..., which="SR")` finds the lowest ones directly.  B^{-1} A is not symmetric: verify with
+    `residuals(A, X, lambda, B)`.  `.solve` is the conjugate-gradient factor (`.solve.cg_info` counts its iterations).  The inner
+    `tol` should be at least 100 times tighter than the outer one (`api.cg_operator`)."""
+    solve = api.cg_operator(B, **cg)
+    op = api.product_operator(solve, A, ctx=solve.ctx)
+    op.solve = solve
+    return op
+
+
 def b_orthonormal_operator(A, L, ctx: api.Context | None = None):
     """The reference's recipe for B-orthonormal Schur vectors (docs/src/index.md:306-352), B = L L* with a sparse
     lower-triangular L (its Cholesky factor): returns `(operator, back)` with operator = C = L^{-1} A L^{-*} -- three device

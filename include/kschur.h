@@ -433,6 +433,34 @@ int ks_operator_chebyshev(ks_ctx* ctx, ks_operator* A, int degree, double center
  * creation by the path they took: fused into the product's launch / product plus streaming pass.  A filter counts the steps of
  * its own applications; any other operator the steps run on it (through a filter or through ks_debug_apply_clenshaw). */
 int ks_operator_chebyshev_info(const ks_operator* op, int* degree, int* temporaries, int64_t* fused_steps, int64_t* generic_steps);
+/* (xiv) Conjugate-gradient solve:  y ~ (A - shift I)^-1 x  for a Hermitian positive definite A - shift I, with nothing but products of
+ * A -- the inner iterative solver of the reference's "LinearMap around a solve" (docs/src/index.md:234-259, and :273-287 for the
+ * pencil) for operators that have nothing to factor: M^-1 K of matrix-free finite elements (ks_operator_product of this operator on M
+ * and K), (A - shift)^-1 with the shift below the spectrum.  Every vector stays in HBM and every scalar of the recurrence on the
+ * device:
+ *     y = 0, r = p = x, rho = rho0 = ||x||^2                         (rho0 == 0: y = 0, 0 iterations)
+ *     q = (A - shift) p;  pq = Re p^H q;  alpha = rho / pq;  r -= alpha q;  rho' = ||r||^2;  y += alpha p;
+ *     done if rho' <= tol^2 rho0, else beta = rho' / rho, p = r + beta p, rho = rho'
+ * with the scalar step of ks_host_cg_step.  The product is the Newton step of (viii) with sigma = 1 (fused into the product by every
+ * stored-matrix and grid layout), A's plain product when shift == 0; the rest of an iteration is three kernels that move 16 + 24 + 40
+ * bytes per row in Float64; KS_C64 runs the same kernels on the real view.  The host enqueues `check_every` iterations (0: the
+ * library default, 8), then reads a device record and goes on until done, a failure or maxit: y and the iteration count do not
+ * depend on check_every, and equal inputs give equal bits.  A is BORROWED like a product's factors.  The solve is linear in x only
+ * up to tol * cond(A - shift): an outer eigensolver's Arnoldi relation inherits that, choose tol at least 100 times tighter than
+ * the outer tolerance.
+ * KS_ERR_ARGUMENT: A made on another context; A that cannot be enqueued ahead (a host callback, another solve of this kind, a
+ * product or filter of one); a context of several ranks ("single-GPU contexts only"); tol not in (0, 1); maxit < 1;
+ * check_every < 0; shift not finite.  The operator itself is applied one step per batch, like a host callback.
+ * KS_ERR_OPERATOR at apply time, the operator staying usable: "not positive definite: p^H (A - theta) p = ... at iteration k" (pq not
+ * finite or <= 0), "did not converge: relative residual ... after maxit iterations".  ks_operator_size reports A's nnz,
+ * ks_operator_format 0 / 0 / -1. */
+int ks_operator_cg(ks_ctx* ctx, ks_operator* A, double shift, double tol, int maxit, int check_every /* 0: library default, 8 */,
+                   ks_operator** out);
+/* Counters of a conjugate-gradient operator (xiv; the inner solver of docs/src/index.md:234-259) since its creation: solves, iterations of all of them, iterations and the recurrence's
+ * relative residual sqrt(rho' / rho0) of the last solve, and the largest such residual of any solve (failed ones included).
+ * KS_ERR_ARGUMENT for any other operator. */
+int ks_operator_cg_info(const ks_operator* op, int64_t* applications, int64_t* iterations, int* last_iterations, double* last_relres,
+                        double* worst_relres);
 int ks_operator_destroy(ks_operator* op);
 int ks_operator_size(const ks_operator* op, int64_t* n_local, int64_t* nnz, int* dtype);
 /* Device layout chosen for a stored matrix at upload (mul!(y, A, x), src/expansion.jl:121; all layouts give bit-identical y):
@@ -891,6 +919,14 @@ typedef struct ks_cheb_step {
 } ks_cheb_step;
 int ks_host_chebyshev_plan(int degree, double center, double halfwidth, const double* coeffs /* degree + 1 */,
                            ks_cheb_step* steps /* degree */, int* temporaries);
+/* The scalar step of ks_operator_cg (xiv) without a device (docs/src/index.md:234-259: the inner solver of the shift-invert recipe) --
+ * the function its kernels run, compiled for the host: from rho = ||r||^2, pq = Re p^H (A - theta) p, rho_new = ||r - alpha q||^2 and
+ * stop = tol^2 rho0
+ *     fail   pq not finite, pq <= 0, rho / pq not finite, or rho_new not finite: alpha = beta = 0, done = 0;
+ *     alpha  rho / pq;     done  rho_new <= stop (rho_new == 0 is done for every stop >= 0, without a division);
+ *     beta   rho_new / rho, 0 when done.
+ * Any output pointer may be NULL. */
+int ks_host_cg_step(double rho, double pq, double rho_new, double stop, double* alpha, double* beta, int* done, int* fail);
 /* The plan, the factors and the HOST apply of ks_operator_tridiag_solve without a device (docs/src/index.md:234-259: the
  * factorize / ldiv! pair of the shift-invert recipe): x[:, k] = (T - sigma I)^-1 b[:, k] for nrhs columns (column k at b + k ldb,
  * x + k ldx; b and x distinct), walking exactly the arrays the device kernels read, in their order.  Same refusals as the operator. */
