@@ -227,6 +227,16 @@ class Operator:
         check(_lib.load().ks_operator_cg_info(self._h, C.byref(a), C.byref(it), C.byref(last), C.byref(rel), C.byref(worst)))
         return dict(applications=a.value, iterations=it.value, last_iterations=last.value, last_relres=rel.value, worst_relres=worst.value)
 
+    @property
+    def minres_info(self) -> dict:
+        """Counters of a `minres_operator` since its creation (`ks_operator_minres_info`; ArgumentError for any other operator):
+        solves, iterations of all of them, iterations and the recurrence's relative residual |phibar| / ||b|| of the last solve, and
+        the largest such residual of any solve."""
+        a, it, last = C.c_int64(), C.c_int64(), C.c_int()
+        rel, worst = C.c_double(), C.c_double()
+        check(_lib.load().ks_operator_minres_info(self._h, C.byref(a), C.byref(it), C.byref(last), C.byref(rel), C.byref(worst)))
+        return dict(applications=a.value, iterations=it.value, last_iterations=last.value, last_relres=rel.value, worst_relres=worst.value)
+
     def close(self):
         # never touch a handle whose context is already gone (interpreter shutdown order is arbitrary)
         if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
@@ -569,6 +579,49 @@ def cg_operator(A: Operator, shift=0.0, tol=1e-13, maxit=1000, check_every=0, ct
     ctx = ctx or A.ctx
     h = C.c_void_p()
     check(_lib.load().ks_operator_cg(ctx._h, A._h, float(shift), float(tol), int(maxit), int(check_every), C.byref(h)))
+    op = Operator(ctx, h, A.shape, A.dtype, keep=(A,))
+    op.base = A
+    return op
+
+
+def host_minres_step(alpha, beta, beta_new, c, s, c_prev, s_prev, phibar, stop):
+    """(eps, delta, gamma, c', s', phi, phibar', done, fail) of one MINRES iteration as `minres_operator`'s kernels decide it
+    (`ks_host_minres_step`; no device needed): the column (beta, alpha, beta_new) of the Lanczos matrix through the two previous
+    rotations (c_prev, s_prev), (c, s), the rotation (c', s') that annihilates beta_new with gamma = hypot(gbar, beta_new), the step
+    length phi = c' phibar and the new residual norm phibar' = -s' phibar.  `fail` (alpha, beta_new or gamma not finite, gamma == 0)
+    zeroes every output but gamma; `done` is |phibar'| <= stop."""
+    out = (C.c_double * 7)()
+    d, f = C.c_int(), C.c_int()
+    args = [float(t) for t in (alpha, beta, beta_new, c, s, c_prev, s_prev, phibar, stop)]
+    check(_lib.load().ks_host_minres_step(*args, C.cast(out, C.c_void_p), C.byref(d), C.byref(f)))
+    return tuple(out) + (bool(d.value), bool(f.value))
+
+
+def minres_operator(A: Operator, shift=0.0, tol=1e-13, maxit=10000, check_every=0, ctx: Context | None = None) -> Operator:
+    """y ~ (A - shift I)^-1 x by MINRES, every vector resident in HBM and every scalar of the recurrence on the device
+    (`ks_operator_minres`): shift-invert for operators that have nothing to factor, with `shift` ANYWHERE on the real axis that is
+    not an eigenvalue -- inside the spectrum too, where `cg_operator` stops at its first negative curvature.
+    `partialschur(minres_operator(A, shift=sigma), which="LM")` finds the eigenvalues of A nearest sigma
+    (`extras.interior_eigenvalues(mu, sigma)` maps them back).  A must be Hermitian (Float64 or ComplexF64; `shift` is real); an A
+    that is not Hermitian is NOT detected -- the three-term recurrence then solves some other problem without a complaint.  The
+    solve stops when the recurrence's residual norm is below `tol` ||x||; `maxit` bounds the iterations (their number grows with
+    the spectrum's width over the distance from `shift` to the nearest eigenvalue), the host looks at the device's record every
+    `check_every` iterations (0: the library default, 8) -- neither the result nor the iteration count depends on it, and equal
+    inputs give equal bits.
+
+    The solve is linear in x only up to tol * cond(A - shift I), and the Arnoldi relation of an outer `partialschur` on this
+    operator inherits that: choose `tol` at least 100 times tighter than the outer tolerance.
+
+    Refused (ArgumentError): an A of another context, one that cannot be enqueued ahead (a host callback, a `cg_operator`, another
+    `minres_operator`, a product or filter of one), a context of several ranks, tol outside (0, 1), maxit < 1, check_every < 0, a
+    shift that is not finite.  At apply time "not finite" (the right-hand side), "singular" (the shift is an eigenvalue) and "did
+    not converge" raise HipError; the operator stays usable.  `.minres_info` counts solves and iterations.  The operator keeps A
+    alive (`.base`); closing it leaves A usable."""
+    if not isinstance(A, Operator):
+        raise ArgumentError(f"minres_operator takes an Operator (as_operator(A) makes one), got {type(A).__name__}")
+    ctx = ctx or A.ctx
+    h = C.c_void_p()
+    check(_lib.load().ks_operator_minres(ctx._h, A._h, float(shift), float(tol), int(maxit), int(check_every), C.byref(h)))
     op = Operator(ctx, h, A.shape, A.dtype, keep=(A,))
     op.base = A
     return op

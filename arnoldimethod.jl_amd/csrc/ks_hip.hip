@@ -42,6 +42,7 @@ using ksd::kBlock;
 #include "ks_defl_plan.hpp"    // host-only: which locked columns a Newton chain is deflated against
 #include "ks_cheb_plan.hpp"    // host-only: the Clenshaw schedule of a Chebyshev filter
 #include "ks_cg_plan.hpp"      // host-only: the scalar step of the conjugate-gradient solve and its device record
+#include "ks_minres_plan.hpp"  // host-only: the scalar step of the MINRES solve (Lanczos column, rotations, stopping test) and its record
 #include "ks_halo.hpp"       // ... uploaded: ghost vector, transport buffers, the exchange in front of a product
 #include "ks_operators.hpp"  // ks_operator and its layouts
 #include "ks_sptrsv.hpp"     // shift-invert operator from triangular factors (sparse triangular solves)
@@ -49,6 +50,7 @@ using ksd::kBlock;
 #include "ks_product.hpp"    // product of operators: generalized problems composed in HBM
 #include "ks_cheb.hpp"       // Chebyshev polynomial filter p(A): Clenshaw steps through the operator's apply_clenshaw
 #include "ks_cg.hpp"         // conjugate-gradient solve (A - theta)^-1: fused vector kernels, scalars and the stopping test on the device
+#include "ks_minres.hpp"     // MINRES solve (A - theta)^-1 for theta inside the spectrum: the same protocol around a Lanczos recurrence
 #include "ks_grid.hpp"       // matrix-free grid operator: stencil taps in the kernel arguments plus a per-point diagonal
 #include "ks_grid_var.hpp"   // ... with a cell-centred coefficient: the link entries formed in registers from c
 #include "ks_grid_box.hpp"   // ... with the diagonal neighbours: the 9- / 27-point box stencil
@@ -456,6 +458,29 @@ int ks_operator_cg_info(const ks_operator* op, int64_t* applications, int64_t* i
     KS_REQUIRE(op, KS_ERR_ARGUMENT, "null operator");
     const CgOp* c = dynamic_cast<const CgOp*>(op);
     KS_REQUIRE(c, KS_ERR_ARGUMENT, "ks_operator_cg_info: not an operator made by ks_operator_cg");
+    if (applications) *applications = c->applications;
+    if (iterations) *iterations = c->iterations;
+    if (last_iterations) *last_iterations = c->last_iterations;
+    if (last_relres) *last_relres = c->last_relres;
+    if (worst_relres) *worst_relres = c->worst_relres;
+  });
+}
+
+int ks_operator_minres(ks_ctx* ctx, ks_operator* A, double shift, double tol, int maxit, int check_every, ks_operator** out) {
+  return guarded([&] {
+    KS_REQUIRE(ctx && out && A, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, "ks_operator_minres: single-GPU contexts only (the reductions of the solve are not summed across ranks)");
+    ctx->use();
+    *out = make_minres(ctx, A, shift, tol, maxit, check_every);
+  });
+}
+
+int ks_operator_minres_info(const ks_operator* op, int64_t* applications, int64_t* iterations, int* last_iterations, double* last_relres,
+                            double* worst_relres) {
+  return guarded([&] {
+    KS_REQUIRE(op, KS_ERR_ARGUMENT, "null operator");
+    const MinresOp* c = dynamic_cast<const MinresOp*>(op);
+    KS_REQUIRE(c, KS_ERR_ARGUMENT, "ks_operator_minres_info: not an operator made by ks_operator_minres");
     if (applications) *applications = c->applications;
     if (iterations) *iterations = c->iterations;
     if (last_iterations) *last_iterations = c->last_iterations;
@@ -1743,6 +1768,19 @@ int ks_host_cg_step(double rho, double pq, double rho_new, double stop, double* 
     if (beta) *beta = s.beta;
     if (done) *done = s.done;
     if (fail) *fail = s.fail;
+  });
+}
+
+int ks_host_minres_step(double alpha, double beta, double beta_new, double c, double s, double c_prev, double s_prev, double phibar,
+                        double stop, double* out /* eps, delta, gamma, c, s, phi, phibar */, int* done, int* fail) {
+  return guarded([&] {
+    const MrStep r = mr_step(alpha, beta, beta_new, c, s, c_prev, s_prev, phibar, stop);
+    if (out) {
+      const double v[7] = {r.eps, r.delta, r.gamma, r.c, r.s, r.phi, r.phibar};
+      for (int i = 0; i < 7; ++i) out[i] = v[i];
+    }
+    if (done) *done = r.done;
+    if (fail) *fail = r.fail;
   });
 }
 

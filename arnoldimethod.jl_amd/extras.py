@@ -183,6 +183,14 @@ def generalized_cg_operator(A: api.Operator, B: api.Operator, **cg) -> api.Opera
     return op
 
 
+def interior_eigenvalues(mu, shift):
+    """lambda = shift + 1 / mu: the eigenvalues of A from the eigenvalues mu = 1 / (lambda - shift) of a shift-invert operator
+    (`api.minres_operator(A, shift=...)`, `api.cg_operator`, `sparse_shift_invert`) -- the back-transformation of the reference's
+    recipe (docs/src/index.md:234-259).  The largest |mu| are the eigenvalues nearest `shift`.  Real input stays real."""
+    mu = np.asarray(mu)
+    return shift + 1.0 / mu
+
+
 def b_orthonormal_operator(A, L, ctx: api.Context | None = None):
     """The reference's recipe for B-orthonormal Schur vectors (docs/src/index.md:306-352), B = L L* with a sparse
     lower-triangular L (its Cholesky factor): returns `(operator, back)` with operator = C = L^{-1} A L^{-*} -- three device

@@ -461,6 +461,28 @@ int ks_operator_cg(ks_ctx* ctx, ks_operator* A, double shift, double tol, int ma
  * KS_ERR_ARGUMENT for any other operator. */
 int ks_operator_cg_info(const ks_operator* op, int64_t* applications, int64_t* iterations, int* last_iterations, double* last_relres,
                         double* worst_relres);
+/* (xv) MINRES solve:  y ~ (A - shift I)^-1 x  for a Hermitian A and any real shift that is not an eigenvalue -- inside the spectrum
+ * too, where (xiv) stops at its first negative curvature: shift-invert (docs/src/index.md:234-259) for operators that have nothing
+ * to factor.  A sibling of (xiv) at every layer: the same products, record protocol, chunked host loop and determinism, around a
+ * three-term Lanczos recurrence and a running QR of its tridiagonal matrix:
+ *     y = 0, beta1 = ||x||, v = x / beta1, v_ = w_ = w__ = 0, beta = 0, (c, s) = (c_, s_) = (1, 0), phibar = beta1
+ *     q = (A - shift) v;  alpha = Re v^H q;  r = q - beta v_ - alpha v;  beta' = ||r||;
+ *     (eps, delta, gamma, c', s', phi, phibar') = ks_host_minres_step(alpha, beta, beta', c, s, c_, s_, phibar, tol beta1);
+ *     w = (v - eps w__ - delta w_) / gamma;  y += phi w;  done if |phibar'| <= tol beta1, else v_ <- v, v <- r / beta', ...
+ * |phibar| is the residual norm of the recurrence; it never increases.  Beside the product an iteration is three kernels that move
+ * 16 + 32 + 64 bytes per row in Float64; KS_C64 runs the same kernels on the real view.  A that is not Hermitian is NOT detected.
+ * Arguments, refusals (KS_ERR_ARGUMENT) and check_every as for ks_operator_cg; A is BORROWED; choose tol at least 100 times tighter
+ * than an outer eigensolver's tolerance.
+ * KS_ERR_OPERATOR at apply time, the operator staying usable: "the right-hand side is not finite", "singular: gamma = ... at
+ * iteration k" (gamma zero or not finite: the shift is an eigenvalue, or the product is not finite), "did not converge: relative
+ * residual ... after maxit iterations". */
+int ks_operator_minres(ks_ctx* ctx, ks_operator* A, double shift, double tol, int maxit, int check_every /* 0: library default, 8 */,
+                       ks_operator** out);
+/* Counters of a MINRES operator (xv) since its creation: solves, iterations of all of them, iterations and the recurrence's relative
+ * residual |phibar| / beta1 of the last solve, and the largest such residual of any solve (failed ones included).  KS_ERR_ARGUMENT
+ * for any other operator. */
+int ks_operator_minres_info(const ks_operator* op, int64_t* applications, int64_t* iterations, int* last_iterations, double* last_relres,
+                            double* worst_relres);
 int ks_operator_destroy(ks_operator* op);
 int ks_operator_size(const ks_operator* op, int64_t* n_local, int64_t* nnz, int* dtype);
 /* Device layout chosen for a stored matrix at upload (mul!(y, A, x), src/expansion.jl:121; all layouts give bit-identical y):
@@ -927,6 +949,16 @@ int ks_host_chebyshev_plan(int degree, double center, double halfwidth, const do
  *     beta   rho_new / rho, 0 when done.
  * Any output pointer may be NULL. */
 int ks_host_cg_step(double rho, double pq, double rho_new, double stop, double* alpha, double* beta, int* done, int* fail);
+/* The scalar step of ks_operator_minres (xv) without a device -- the function its kernels run, compiled for the host: the new column
+ * (beta, alpha, beta_new) of the Lanczos matrix through the rotations (c_prev, s_prev) and (c, s), the rotation that annihilates
+ * beta_new, and the stopping test against stop = tol ||b||:
+ *     eps = s_prev beta;  dbar = c_prev beta;  delta = c dbar + s alpha;  gbar = -s dbar + c alpha;
+ *     gamma = hypot(gbar, beta_new), scaled by the larger of the two so that it overflows only where gamma itself does;
+ *     fail  alpha, beta_new or gamma not finite, or gamma == 0: every output 0 but gamma;
+ *     c' = gbar / gamma;  s' = beta_new / gamma;  phi = c' phibar;  phibar' = -s' phibar;  done  |phibar'| <= stop.
+ * out = {eps, delta, gamma, c', s', phi, phibar'}.  Any output pointer may be NULL. */
+int ks_host_minres_step(double alpha, double beta, double beta_new, double c, double s, double c_prev, double s_prev, double phibar,
+                        double stop, double* out /* 7 */, int* done, int* fail);
 /* The plan, the factors and the HOST apply of ks_operator_tridiag_solve without a device (docs/src/index.md:234-259: the
  * factorize / ldiv! pair of the shift-invert recipe): x[:, k] = (T - sigma I)^-1 b[:, k] for nrhs columns (column k at b + k ldb,
  * x + k ldx; b and x distinct), walking exactly the arrays the device kernels read, in their order.  Same refusals as the operator. */
