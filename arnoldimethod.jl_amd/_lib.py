@@ -106,6 +106,8 @@ PROTOTYPES = {
     "ks_operator_cg_info": [vp, P(i64), P(i64), P(C.c_int), P(dbl), P(dbl)],
     "ks_operator_minres": [vp, vp, dbl, dbl, i32, i32, P(vp)],
     "ks_operator_minres_info": [vp, P(i64), P(i64), P(C.c_int), P(dbl), P(dbl)],
+    "ks_operator_bicgstab": [vp, vp, dbl, dbl, dbl, i32, i32, P(vp)],
+    "ks_operator_bicgstab_info": [vp, P(i64), P(i64), P(C.c_int), P(dbl), P(dbl)],
     "ks_operator_grid": [vp, i32, vp, i32, vp, vp, P(vp)],
     "ks_operator_grid_periodic": [vp, i32, vp, i32, vp, vp, vp, vp, P(vp)],
     "ks_operator_grid_star": [vp, i32, vp, i32, i32, vp, vp, P(vp)],
@@ -154,6 +156,8 @@ PROTOTYPES = {
     "ks_host_chebyshev_plan": [i32, dbl, dbl, vp, vp, P(C.c_int)],
     "ks_host_cg_step": [dbl, dbl, dbl, dbl, P(dbl), P(dbl), P(C.c_int), P(C.c_int)],
     "ks_host_minres_step": [dbl] * 9 + [vp, P(C.c_int), P(C.c_int)],
+    "ks_host_bicgstab_coef": [i32, vp, vp, vp, vp, vp, vp, P(C.c_int)],
+    "ks_host_bicgstab_mr": [i32, dbl, dbl, vp, vp, vp, vp, vp, P(dbl), P(C.c_int)],
     "ks_gemv_t": [vp, i32, i32, vp],
     "ks_gemv_n_sub": [vp, i32, i32, vp],
     "ks_rotate": [vp, i32, i32, i32, vp, i32],

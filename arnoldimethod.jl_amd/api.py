@@ -237,6 +237,16 @@ class Operator:
         check(_lib.load().ks_operator_minres_info(self._h, C.byref(a), C.byref(it), C.byref(last), C.byref(rel), C.byref(worst)))
         return dict(applications=a.value, iterations=it.value, last_iterations=last.value, last_relres=rel.value, worst_relres=worst.value)
 
+    @property
+    def bicgstab_info(self) -> dict:
+        """Counters of a `bicgstab_operator` since its creation (`ks_operator_bicgstab_info`; ArgumentError for any other operator):
+        solves, iterations of all of them (four products each), iterations and the recurrence's relative residual ||r0|| / ||b|| of
+        the last solve, and the largest such residual of any solve."""
+        a, it, last = C.c_int64(), C.c_int64(), C.c_int()
+        rel, worst = C.c_double(), C.c_double()
+        check(_lib.load().ks_operator_bicgstab_info(self._h, C.byref(a), C.byref(it), C.byref(last), C.byref(rel), C.byref(worst)))
+        return dict(applications=a.value, iterations=it.value, last_iterations=last.value, last_relres=rel.value, worst_relres=worst.value)
+
     def close(self):
         # never touch a handle whose context is already gone (interpreter shutdown order is arbitrary)
         if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
@@ -622,6 +632,74 @@ def minres_operator(A: Operator, shift=0.0, tol=1e-13, maxit=10000, check_every=
     ctx = ctx or A.ctx
     h = C.c_void_p()
     check(_lib.load().ks_operator_minres(ctx._h, A._h, float(shift), float(tol), int(maxit), int(check_every), C.byref(h)))
+    op = Operator(ctx, h, A.shape, A.dtype, keep=(A,))
+    op.base = A
+    return op
+
+
+def _scalar_pair(z):
+    z = complex(z)
+    return (C.c_double * 2)(z.real, z.imag)
+
+
+def host_bicgstab_coef(rho0, rho1, alpha, gamma, complex_scalars=None):
+    """(beta, alpha', fail) of one BiCG coefficient step as `bicgstab_operator`'s kernels decide it (`ks_host_bicgstab_coef`; no
+    device needed): beta = alpha rho1 / rho0, alpha' = rho1 / gamma.  fail 1: rho0 zero or not finite, or beta not finite (both
+    outputs 0); fail 2: gamma zero or not finite, or alpha' not finite (alpha' = 0).  Complex arithmetic when any argument is complex
+    (or `complex_scalars` says so): the outputs are then complex, else floats."""
+    args = (rho0, rho1, alpha, gamma)
+    cplx = any(isinstance(t, (complex, np.complexfloating)) for t in args) if complex_scalars is None else bool(complex_scalars)
+    beta, anew, f = (C.c_double * 2)(), (C.c_double * 2)(), C.c_int()
+    pairs = [_scalar_pair(t) for t in args]
+    check(_lib.load().ks_host_bicgstab_coef(int(cplx), *[C.cast(t, C.c_void_p) for t in pairs], C.cast(beta, C.c_void_p), C.cast(anew, C.c_void_p),
+                                            C.byref(f)))
+    if cplx:
+        return complex(beta[0], beta[1]), complex(anew[0], anew[1]), f.value
+    return beta[0], anew[0], f.value
+
+
+def host_bicgstab_mr(g11, g22, g12, h1, h2, complex_scalars=None):
+    """(g1, g2, det, fail) of the two-dimensional minimal-residual step of `bicgstab_operator` (`ks_host_bicgstab_mr`; no device
+    needed): the Hermitian system [g11 g12; conj(g12) g22] g = h by Cramer's rule with det = fma(g11, g22, -|g12|^2).  fail: det
+    zero or not finite, or a quotient not finite (g = 0).  Complex arithmetic when g12, h1 or h2 is complex."""
+    args = (g12, h1, h2)
+    cplx = any(isinstance(t, (complex, np.complexfloating)) for t in args) if complex_scalars is None else bool(complex_scalars)
+    g1, g2, det, f = (C.c_double * 2)(), (C.c_double * 2)(), C.c_double(), C.c_int()
+    pairs = [_scalar_pair(t) for t in args]
+    check(_lib.load().ks_host_bicgstab_mr(int(cplx), float(g11), float(g22), *[C.cast(t, C.c_void_p) for t in pairs], C.cast(g1, C.c_void_p),
+                                          C.cast(g2, C.c_void_p), C.byref(det), C.byref(f)))
+    if cplx:
+        return complex(g1[0], g1[1]), complex(g2[0], g2[1]), det.value, f.value
+    return g1[0], g2[0], det.value, f.value
+
+
+def bicgstab_operator(A: Operator, shift=0.0, tol=1e-13, maxit=10000, check_every=0, ctx: Context | None = None) -> Operator:
+    """y ~ (A - shift I)^-1 x by BiCGStab(2), every vector resident in HBM and every scalar of the recurrence on the device
+    (`ks_operator_bicgstab`): shift-invert for operators that are NOT Hermitian and have nothing to factor -- a grid stencil with a
+    convection term, a `product_operator` chain, a Bloch cell with a complex shift -- where `cg_operator` and `minres_operator` need a
+    Hermitian A.  `partialschur(bicgstab_operator(A, shift=sigma), which="LM")` finds the eigenvalues of A nearest sigma
+    (`extras.interior_eigenvalues(mu, sigma)` maps them back).  Float64 with a real `shift`, or ComplexF64 with a complex one.  An
+    iteration is two BiCG steps and a two-dimensional minimal-residual step, four products; the solve stops when the recurrence's
+    residual norm is below `tol` ||x||, tested after each BiCG step and after the minimal-residual step.  `maxit` bounds the
+    iterations, the host looks at the device's record every `check_every` iterations (0: the library default, 8) -- neither the
+    result nor the iteration count depends on it, and equal inputs give equal bits.
+
+    No preconditioner and no residual replacement: on a shift deep inside a complex spectrum the solve needs hundreds of iterations
+    and the true residual drifts above the recurrence's (README).  The solve is linear in x only up to tol * cond(A - shift I):
+    choose `tol` at least 100 times tighter than the outer tolerance.
+
+    Refused (ArgumentError): an imaginary shift on a Float64 operator (build the operator in ComplexF64), an A of another context,
+    one that cannot be enqueued ahead (a host callback, a `cg_operator`, `minres_operator` or another `bicgstab_operator`, a product
+    or filter of one), a context of several ranks, tol outside (0, 1), maxit < 1, check_every < 0, a shift that is not finite.  At
+    apply time "not finite" (the right-hand side), "breakdown" (rho, gamma or det G zero or not finite: the shift is an eigenvalue)
+    and "did not converge" raise HipError; the operator stays usable.  `.bicgstab_info` counts solves and iterations.  The operator
+    keeps A alive (`.base`); closing it leaves A usable."""
+    if not isinstance(A, Operator):
+        raise ArgumentError(f"bicgstab_operator takes an Operator (as_operator(A) makes one), got {type(A).__name__}")
+    ctx = ctx or A.ctx
+    h = C.c_void_p()
+    z = complex(shift)
+    check(_lib.load().ks_operator_bicgstab(ctx._h, A._h, z.real, z.imag, float(tol), int(maxit), int(check_every), C.byref(h)))
     op = Operator(ctx, h, A.shape, A.dtype, keep=(A,))
     op.base = A
     return op

@@ -43,6 +43,7 @@ using ksd::kBlock;
 #include "ks_cheb_plan.hpp"    // host-only: the Clenshaw schedule of a Chebyshev filter
 #include "ks_cg_plan.hpp"      // host-only: the scalar step of the conjugate-gradient solve and its device record
 #include "ks_minres_plan.hpp"  // host-only: the scalar step of the MINRES solve (Lanczos column, rotations, stopping test) and its record
+#include "ks_bicgstab_plan.hpp"  // host-only: the scalar steps of the BiCGStab(2) solve (BiCG coefficients, 2 x 2 MR solve, stage tests) and its record
 #include "ks_halo.hpp"       // ... uploaded: ghost vector, transport buffers, the exchange in front of a product
 #include "ks_operators.hpp"  // ks_operator and its layouts
 #include "ks_sptrsv.hpp"     // shift-invert operator from triangular factors (sparse triangular solves)
@@ -51,6 +52,7 @@ using ksd::kBlock;
 #include "ks_cheb.hpp"       // Chebyshev polynomial filter p(A): Clenshaw steps through the operator's apply_clenshaw
 #include "ks_cg.hpp"         // conjugate-gradient solve (A - theta)^-1: fused vector kernels, scalars and the stopping test on the device
 #include "ks_minres.hpp"     // MINRES solve (A - theta)^-1 for theta inside the spectrum: the same protocol around a Lanczos recurrence
+#include "ks_bicgstab.hpp"   // BiCGStab(2) solve (A - theta)^-1 for operators that are not Hermitian: the same protocol, scalars of the operator's type
 #include "ks_grid.hpp"       // matrix-free grid operator: stencil taps in the kernel arguments plus a per-point diagonal
 #include "ks_grid_var.hpp"   // ... with a cell-centred coefficient: the link entries formed in registers from c
 #include "ks_grid_box.hpp"   // ... with the diagonal neighbours: the 9- / 27-point box stencil
@@ -481,6 +483,29 @@ int ks_operator_minres_info(const ks_operator* op, int64_t* applications, int64_
     KS_REQUIRE(op, KS_ERR_ARGUMENT, "null operator");
     const MinresOp* c = dynamic_cast<const MinresOp*>(op);
     KS_REQUIRE(c, KS_ERR_ARGUMENT, "ks_operator_minres_info: not an operator made by ks_operator_minres");
+    if (applications) *applications = c->applications;
+    if (iterations) *iterations = c->iterations;
+    if (last_iterations) *last_iterations = c->last_iterations;
+    if (last_relres) *last_relres = c->last_relres;
+    if (worst_relres) *worst_relres = c->worst_relres;
+  });
+}
+
+int ks_operator_bicgstab(ks_ctx* ctx, ks_operator* A, double shift_re, double shift_im, double tol, int maxit, int check_every, ks_operator** out) {
+  return guarded([&] {
+    KS_REQUIRE(ctx && out && A, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, "ks_operator_bicgstab: single-GPU contexts only (the reductions of the solve are not summed across ranks)");
+    ctx->use();
+    *out = make_bicgstab(ctx, A, shift_re, shift_im, tol, maxit, check_every);
+  });
+}
+
+int ks_operator_bicgstab_info(const ks_operator* op, int64_t* applications, int64_t* iterations, int* last_iterations, double* last_relres,
+                              double* worst_relres) {
+  return guarded([&] {
+    KS_REQUIRE(op, KS_ERR_ARGUMENT, "null operator");
+    const BicgstabOp* c = dynamic_cast<const BicgstabOp*>(op);
+    KS_REQUIRE(c, KS_ERR_ARGUMENT, "ks_operator_bicgstab_info: not an operator made by ks_operator_bicgstab");
     if (applications) *applications = c->applications;
     if (iterations) *iterations = c->iterations;
     if (last_iterations) *last_iterations = c->last_iterations;
@@ -1781,6 +1806,37 @@ int ks_host_minres_step(double alpha, double beta, double beta_new, double c, do
     }
     if (done) *done = r.done;
     if (fail) *fail = r.fail;
+  });
+}
+
+int ks_host_bicgstab_coef(int is_complex, const double* rho0, const double* rho1, const double* alpha, const double* gamma, double* beta,
+                          double* alpha_new, int* fail) {
+  return guarded([&] {
+    KS_REQUIRE(rho0 && rho1 && alpha && gamma, KS_ERR_ARGUMENT, "null argument");
+    auto run = [&](auto z) {
+      using S = decltype(z);
+      const BsCoef<S> c = bs_coef(bs_load<S>(rho0), bs_load<S>(rho1), bs_load<S>(alpha), bs_load<S>(gamma));
+      if (beta) bs_store(beta, c.beta);
+      if (alpha_new) bs_store(alpha_new, c.alpha);
+      if (fail) *fail = c.fail;
+    };
+    if (is_complex) run(BsZ{0.0, 0.0}); else run(0.0);
+  });
+}
+
+int ks_host_bicgstab_mr(int is_complex, double g11, double g22, const double* g12, const double* h1, const double* h2, double* g1, double* g2,
+                        double* det, int* fail) {
+  return guarded([&] {
+    KS_REQUIRE(g12 && h1 && h2, KS_ERR_ARGUMENT, "null argument");
+    auto run = [&](auto z) {
+      using S = decltype(z);
+      const BsMr<S> m = bs_mr(g11, g22, bs_load<S>(g12), bs_load<S>(h1), bs_load<S>(h2));
+      if (g1) bs_store(g1, m.g1);
+      if (g2) bs_store(g2, m.g2);
+      if (det) *det = m.det;
+      if (fail) *fail = m.fail;
+    };
+    if (is_complex) run(BsZ{0.0, 0.0}); else run(0.0);
   });
 }
 

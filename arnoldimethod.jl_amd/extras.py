@@ -185,8 +185,10 @@ def generalized_cg_operator(A: api.Operator, B: api.Operator, **cg) -> api.Opera
 
 def interior_eigenvalues(mu, shift):
     """lambda = shift + 1 / mu: the eigenvalues of A from the eigenvalues mu = 1 / (lambda - shift) of a shift-invert operator
-    (`api.minres_operator(A, shift=...)`, `api.cg_operator`, `sparse_shift_invert`) -- the back-transformation of the reference's
-    recipe (docs/src/index.md:234-259).  The largest |mu| are the eigenvalues nearest `shift`.  Real input stays real."""
+    (`api.minres_operator(A, shift=...)`, `api.cg_operator`, `api.bicgstab_operator`, `sparse_shift_invert`) -- the
+    back-transformation of the reference's recipe (docs/src/index.md:234-259).  The largest |mu| are the eigenvalues nearest
+    `shift`.  Real input stays real; a complex mu (the pairs of an operator that is not Hermitian) or a complex shift gives complex
+    eigenvalues."""
     mu = np.asarray(mu)
     return shift + 1.0 / mu
 

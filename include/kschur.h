@@ -483,6 +483,36 @@ int ks_operator_minres(ks_ctx* ctx, ks_operator* A, double shift, double tol, in
  * for any other operator. */
 int ks_operator_minres_info(const ks_operator* op, int64_t* applications, int64_t* iterations, int* last_iterations, double* last_relres,
                             double* worst_relres);
+/* (xvi) BiCGStab(2) solve:  y ~ (A - shift I)^-1 x  for ANY operator A that can be enqueued ahead -- not Hermitian (a convection
+ * term), or with a complex shift: shift-invert (docs/src/index.md:234-259) for general operators that have nothing to factor, where
+ * (xiv) and (xv) need a Hermitian A.  KS_F64 with a real shift (shift_im must be 0), or KS_C64 with a complex one.  A sibling of
+ * (xiv) and (xv) at every layer: the same products, record protocol, chunked host loop and determinism, around two BiCG steps and
+ * a two-dimensional minimal-residual step per iteration (four products); <a, c> = a^H c, rt = x is read only:
+ *     y = 0, r0 = x, u0 = 0, rho0 = 1, alpha = 0, omega = 1, beta1 = ||x||
+ *     rho0 <- -omega rho0
+ *     rho1 = <rt, r0>; beta = alpha rho1 / rho0; rho0 <- rho1; u0 <- r0 - beta u0; u1 = (A - shift) u0; gamma = <rt, u1>;
+ *       alpha = rho0 / gamma; r0 -= alpha u1; y += alpha u0;                          done if ||r0|| <= tol beta1   (stage 1)
+ *     r1 = (A - shift) r0; rho1 = <rt, r1>; beta = alpha rho1 / rho0; rho0 <- rho1; u0 <- r0 - beta u0; u1 <- r1 - beta u1;
+ *       u2 = (A - shift) u1; gamma = <rt, u2>; alpha = rho0 / gamma; r0 -= alpha u1; r1 -= alpha u2; y += alpha u0;
+ *                                                                                      done if ||r0|| <= tol beta1   (stage 2)
+ *     r2 = (A - shift) r1; G = [<r1,r1> <r1,r2>; <r2,r1> <r2,r2>], h = [<r1,r0>; <r2,r0>], G g = h;
+ *       y += g1 r0 + g2 r1; r0 -= g1 r1 + g2 r2; u0 -= g1 u1 + g2 u2; omega = g2;     done if ||r0|| <= tol beta1   (stage 3)
+ * (ks_host_bicgstab_coef and ks_host_bicgstab_mr are the scalar steps).  Beside the products an iteration is nine streaming kernels
+ * that move 352 bytes per row in Float64 (88 per product), templates on the scalar type: the scalars of KS_C64 are complex.
+ * Arguments, refusals (KS_ERR_ARGUMENT) and check_every as for ks_operator_cg, and: an imaginary shift on a KS_F64 operator (build
+ * the operator in KS_C64).  A is BORROWED; the operator owns six vectors.  No preconditioner; the residual is the recurrence's, which
+ * drifts from the true one on hard shifts (deep inside a complex spectrum); choose tol at least 100 times tighter than an outer
+ * eigensolver's tolerance.
+ * KS_ERR_OPERATOR at apply time, the operator staying usable: "the right-hand side is not finite", "breakdown: rho | gamma | det G =
+ * ... in stage s at iteration k" (zero or not finite: the shift is an eigenvalue, the shadow residual has lost the Krylov space, or
+ * the product is not finite), "did not converge: relative residual ... after maxit iterations". */
+int ks_operator_bicgstab(ks_ctx* ctx, ks_operator* A, double shift_re, double shift_im, double tol, int maxit,
+                         int check_every /* 0: library default, 8 */, ks_operator** out);
+/* Counters of a BiCGStab(2) operator (xvi) since its creation: solves, iterations of all of them (one iteration = four products; one
+ * that ended in stage 1 or 2 counts), iterations and the recurrence's relative residual ||r0|| / beta1 of the last solve, and the
+ * largest such residual of any solve (failed ones included).  KS_ERR_ARGUMENT for any other operator. */
+int ks_operator_bicgstab_info(const ks_operator* op, int64_t* applications, int64_t* iterations, int* last_iterations, double* last_relres,
+                              double* worst_relres);
 int ks_operator_destroy(ks_operator* op);
 int ks_operator_size(const ks_operator* op, int64_t* n_local, int64_t* nnz, int* dtype);
 /* Device layout chosen for a stored matrix at upload (mul!(y, A, x), src/expansion.jl:121; all layouts give bit-identical y):
@@ -959,6 +989,22 @@ int ks_host_cg_step(double rho, double pq, double rho_new, double stop, double* 
  * out = {eps, delta, gamma, c', s', phi, phibar'}.  Any output pointer may be NULL. */
 int ks_host_minres_step(double alpha, double beta, double beta_new, double c, double s, double c_prev, double s_prev, double phibar,
                         double stop, double* out /* 7 */, int* done, int* fail);
+/* The scalar steps of ks_operator_bicgstab (xvi) without a device -- the functions its kernels run, compiled for the host.  Every
+ * scalar is a pair {re, im}; with is_complex == 0 the imaginary parts are ignored on input and 0 on output.  Only + - * /, sqrt and
+ * explicit fma; a complex quotient a / b is a conj(b) / |b|^2.
+ * ks_host_bicgstab_coef, one BiCG coefficient step:
+ *     fail 1  rho0 zero or not finite, or beta not finite:   beta = alpha_new = 0;
+ *     beta = alpha rho1 / rho0;
+ *     fail 2  gamma zero or not finite, or alpha_new not finite:   alpha_new = 0 (beta stands);
+ *     alpha_new = rho1 / gamma.
+ * ks_host_bicgstab_mr, the Hermitian 2 x 2 minimal-residual solve [g11 g12; conj(g12) g22] g = h by Cramer's rule:
+ *     det = fma(g11, g22, -|g12|^2);   fail 1  det zero or not finite, or a quotient not finite:   g = 0;
+ *     g1 = (g22 h1 - g12 h2) / det;   g2 = (g11 h2 - conj(g12) h1) / det.
+ * Any output pointer may be NULL. */
+int ks_host_bicgstab_coef(int is_complex, const double* rho0, const double* rho1, const double* alpha, const double* gamma, double* beta,
+                          double* alpha_new, int* fail);
+int ks_host_bicgstab_mr(int is_complex, double g11, double g22, const double* g12, const double* h1, const double* h2, double* g1, double* g2,
+                        double* det, int* fail);
 /* The plan, the factors and the HOST apply of ks_operator_tridiag_solve without a device (docs/src/index.md:234-259: the
  * factorize / ldiv! pair of the shift-invert recipe): x[:, k] = (T - sigma I)^-1 b[:, k] for nrhs columns (column k at b + k ldb,
  * x + k ldx; b and x distinct), walking exactly the arrays the device kernels read, in their order.  Same refusals as the operator. */
