@@ -16,6 +16,7 @@ KS_OK, KS_ERR_ARGUMENT, KS_ERR_DIMENSION, KS_ERR_HIP, KS_ERR_RCCL, KS_ERR_QR, KS
 KS_F64, KS_C64 = 0, 1
 KS_I32, KS_I64 = 0, 1
 KS_CSR, KS_CSC = 0, 1
+KS_PCG_PATH_GENERIC, KS_PCG_PATH_JACOBI = 0, 1
 LAYOUTS = {-1: "none", 0: "csr", 1: "csr-vi", 2: "csr-dvi", 3: "sell", 4: "sell-vi", 5: "stencil", 6: "csr-cb"}
 PLAN_FACTS = ("ptr64", "ni", "nblk", "nlong", "row_gather", "nslices", "sell_entries", "ncolblocks", "cb_rpt", "cb_ni", "nstencil",
               "nstencil_local", "stencil_mask_bytes", "ndvi", "dvi_unroll")  # KS_PLAN_* of include/kschur.h
@@ -108,6 +109,9 @@ PROTOTYPES = {
     "ks_operator_minres_info": [vp, P(i64), P(i64), P(C.c_int), P(dbl), P(dbl)],
     "ks_operator_bicgstab": [vp, vp, dbl, dbl, dbl, i32, i32, P(vp)],
     "ks_operator_bicgstab_info": [vp, P(i64), P(i64), P(C.c_int), P(dbl), P(dbl)],
+    "ks_operator_pcg": [vp, vp, vp, dbl, dbl, i32, i32, P(vp)],
+    "ks_operator_pcg_info": [vp, P(i64), P(i64), P(C.c_int), P(dbl), P(dbl), P(i64), P(C.c_int)],
+    "ks_operator_diagonal": [vp, i64, i32, vp, P(vp)],
     "ks_operator_grid": [vp, i32, vp, i32, vp, vp, P(vp)],
     "ks_operator_grid_periodic": [vp, i32, vp, i32, vp, vp, vp, vp, P(vp)],
     "ks_operator_grid_star": [vp, i32, vp, i32, i32, vp, vp, P(vp)],
@@ -155,6 +159,7 @@ PROTOTYPES = {
     "ks_debug_apply_clenshaw": [vp, vp, i32, i32, i32, i32, dbl, dbl, dbl, dbl, i32],
     "ks_host_chebyshev_plan": [i32, dbl, dbl, vp, vp, P(C.c_int)],
     "ks_host_cg_step": [dbl, dbl, dbl, dbl, P(dbl), P(dbl), P(C.c_int), P(C.c_int)],
+    "ks_host_pcg_step": [dbl, dbl, dbl, dbl, dbl, P(dbl), P(dbl), P(C.c_int), P(C.c_int)],
     "ks_host_minres_step": [dbl] * 9 + [vp, P(C.c_int), P(C.c_int)],
     "ks_host_bicgstab_coef": [i32, vp, vp, vp, vp, vp, vp, P(C.c_int)],
     "ks_host_bicgstab_mr": [i32, dbl, dbl, vp, vp, vp, vp, vp, P(dbl), P(C.c_int)],

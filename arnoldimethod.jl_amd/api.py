@@ -228,6 +228,18 @@ class Operator:
         return dict(applications=a.value, iterations=it.value, last_iterations=last.value, last_relres=rel.value, worst_relres=worst.value)
 
     @property
+    def pcg_info(self) -> dict:
+        """Counters of a `pcg_operator` since its creation (`ks_operator_pcg_info`; ArgumentError for any other operator): the
+        fields of `cg_info`, `preconditioner_applications` (generic path: launches of M, those behind the end of a solve inside a
+        chunk included; Jacobi path: one per solve and one per iteration) and `path`, "jacobi" or "generic"."""
+        a, it, last, pa, path = C.c_int64(), C.c_int64(), C.c_int(), C.c_int64(), C.c_int()
+        rel, worst = C.c_double(), C.c_double()
+        check(_lib.load().ks_operator_pcg_info(self._h, C.byref(a), C.byref(it), C.byref(last), C.byref(rel), C.byref(worst), C.byref(pa),
+                                               C.byref(path)))
+        return dict(applications=a.value, iterations=it.value, last_iterations=last.value, last_relres=rel.value, worst_relres=worst.value,
+                    preconditioner_applications=pa.value, path="jacobi" if path.value == _lib.KS_PCG_PATH_JACOBI else "generic")
+
+    @property
     def minres_info(self) -> dict:
         """Counters of a `minres_operator` since its creation (`ks_operator_minres_info`; ArgumentError for any other operator):
         solves, iterations of all of them, iterations and the recurrence's relative residual |phibar| / ||b|| of the last solve, and
@@ -575,7 +587,8 @@ def cg_operator(A: Operator, shift=0.0, tol=1e-13, maxit=1000, check_every=0, ct
     finite elements (`extras.generalized_cg_operator`), any Hermitian operator with `shift` below its spectrum.  A - shift I must be
     Hermitian positive definite (Float64 or ComplexF64; `shift` is real).  The solve stops when the recurrence's residual is below
     `tol` ||x||; `maxit` bounds the iterations, the host looks at the device's record every `check_every` iterations (0: the
-    library default, 8) -- neither the result nor the iteration count depends on it, and equal inputs give equal bits.
+    library default, 8) -- neither the result nor the iteration count depends on it, and equal inputs give equal bits.  For an
+    ill-conditioned operator (a coefficient jump, an anisotropic grid) `pcg_operator` is this solve with a preconditioner.
 
     The solve is linear in x only up to tol * cond(A - shift I), and the Arnoldi relation of an outer `partialschur` on this
     operator inherits that: choose `tol` at least 100 times tighter than the outer tolerance.
@@ -591,6 +604,70 @@ def cg_operator(A: Operator, shift=0.0, tol=1e-13, maxit=1000, check_every=0, ct
     check(_lib.load().ks_operator_cg(ctx._h, A._h, float(shift), float(tol), int(maxit), int(check_every), C.byref(h)))
     op = Operator(ctx, h, A.shape, A.dtype, keep=(A,))
     op.base = A
+    return op
+
+
+PCG_FAIL = {0: None, 1: "right-hand side", 2: "curvature", 3: "preconditioner", 4: "residual"}   # the reason codes of ks_host_pcg_step
+
+
+def host_pcg_step(tau, pq, rho_new, stop, tau_new):
+    """(alpha, beta, done, fail) of one preconditioned conjugate-gradient iteration as `pcg_operator`'s kernels decide it
+    (`ks_host_pcg_step`; no device needed): from tau = Re r^H M r, pq = Re p^H (A - shift) p, rho_new = ||r - alpha q||^2,
+    stop = tol^2 ||b||^2 and tau_new = Re r^H M r after the step.  `fail` is 0 or a reason code (`PCG_FAIL`): 2, pq not finite or <= 0
+    or alpha not finite, and 4, rho_new not finite, give alpha = beta = 0; `done` is rho_new <= stop and gives beta = 0 without a look
+    at tau_new; otherwise 3, tau_new not finite or <= 0 or beta not finite, gives beta = 0 and leaves alpha."""
+    a, b, d, f = C.c_double(), C.c_double(), C.c_int(), C.c_int()
+    check(_lib.load().ks_host_pcg_step(float(tau), float(pq), float(rho_new), float(stop), float(tau_new), C.byref(a), C.byref(b), C.byref(d),
+                                       C.byref(f)))
+    return a.value, b.value, bool(d.value), f.value
+
+
+def diagonal_operator(d, dtype=None, ctx: Context | None = None) -> Operator:
+    """y = d o x for a real vector d of n finite entries, on Float64 (the default) or ComplexF64 vectors (`ks_operator_diagonal`):
+    a lumped mass matrix or its inverse (M^-1 K as `product_operator(diagonal_operator(1 / m), K)`), a scaling, the Jacobi
+    preconditioner of `pcg_operator` (`extras.jacobi_preconditioner`).  One streaming kernel, 24 bytes per row in Float64; usable
+    wherever an operator is.  Negative entries and zeros are allowed: it is an operator, not only a preconditioner."""
+    ctx = ctx or default_context()
+    v = np.asarray(d)
+    if v.ndim != 1 or v.dtype.kind not in "fiu":
+        raise ArgumentError(f"d must be a 1-D sequence of real numbers, got shape {v.shape}, dtype {v.dtype}")
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    if not np.all(np.isfinite(v)):
+        raise ArgumentError(f"d must be finite (entry {int(np.flatnonzero(~np.isfinite(v))[0])} is not)")
+    dt = np.dtype(np.float64 if dtype is None else dtype)
+    if dt not in (np.dtype(np.float64), np.dtype(np.complex128)):
+        raise ArgumentError(f"element type must be float64 or complex128, not {dt}")
+    h = C.c_void_p()
+    check(_lib.load().ks_operator_diagonal(ctx._h, v.size, _dtype_code(dt), v.ctypes.data if v.size else None, C.byref(h)))
+    op = Operator(ctx, h, (v.size, v.size), dt)
+    op.diagonal = v
+    return op
+
+
+def pcg_operator(A: Operator, M: Operator, shift=0.0, tol=1e-13, maxit=1000, check_every=0, ctx: Context | None = None) -> Operator:
+    """y ~ (A - shift I)^-1 x by PRECONDITIONED conjugate gradients with the device operator M ~ (A - shift I)^-1, every vector
+    resident in HBM and every scalar of the recurrence on the device (`ks_operator_pcg`): `cg_operator` for the operators it cannot
+    reach -- a coefficient jump (`extras.jacobi_preconditioner`: 72 iterations where plain conjugate gradients take 519), an
+    anisotropic grid (`extras.line_preconditioner`: 16 against 94), the caller's incomplete factors (`lu_operator`).  A - shift I and M
+    must be Hermitian positive definite and M the same linear map in every iteration; build M for A - shift I, not for A.  The
+    stopping test, `tol`, `maxit` and `check_every` are `cg_operator`'s (the 2-norm of the recurrence's residual below `tol` ||x||),
+    and so is the advice on an outer `partialschur`.  A `diagonal_operator` as M is fused into the solver's own kernels (three
+    launches per iteration, no extra vector; KS_PCG_FUSED=0 runs it like any other M, with the same bits).  A
+    `chebyshev_operator` of A as M works but does not reduce the number of products.
+
+    Refused (ArgumentError): what `cg_operator` refuses, an M that is not an Operator, of another context, element type or size, or one
+    that cannot be enqueued ahead (a host callback, a `cg_operator` or one of its siblings: that would need flexible conjugate
+    gradients).  At apply time "not positive definite", "the preconditioner is not positive definite" and "did not converge" raise
+    HipError; the operator stays usable.  `.pcg_info` counts solves, iterations and applications of M.  The operator keeps A and M
+    alive (`.base`, `.preconditioner`); closing it leaves them usable."""
+    for what, op in (("an Operator (as_operator(A) makes one)", A), ("an Operator as preconditioner", M)):
+        if not isinstance(op, Operator):
+            raise ArgumentError(f"pcg_operator takes {what}, got {type(op).__name__}")
+    ctx = ctx or A.ctx
+    h = C.c_void_p()
+    check(_lib.load().ks_operator_pcg(ctx._h, A._h, M._h, float(shift), float(tol), int(maxit), int(check_every), C.byref(h)))
+    op = Operator(ctx, h, A.shape, A.dtype, keep=(A, M))
+    op.base, op.preconditioner = A, M
     return op
 
 

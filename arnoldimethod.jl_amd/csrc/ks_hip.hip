@@ -42,6 +42,7 @@ using ksd::kBlock;
 #include "ks_defl_plan.hpp"    // host-only: which locked columns a Newton chain is deflated against
 #include "ks_cheb_plan.hpp"    // host-only: the Clenshaw schedule of a Chebyshev filter
 #include "ks_cg_plan.hpp"      // host-only: the scalar step of the conjugate-gradient solve and its device record
+#include "ks_pcg_plan.hpp"     // host-only: the scalar steps of the preconditioned conjugate-gradient solve and its device record
 #include "ks_minres_plan.hpp"  // host-only: the scalar step of the MINRES solve (Lanczos column, rotations, stopping test) and its record
 #include "ks_bicgstab_plan.hpp"  // host-only: the scalar steps of the BiCGStab(2) solve (BiCG coefficients, 2 x 2 MR solve, stage tests) and its record
 #include "ks_halo.hpp"       // ... uploaded: ghost vector, transport buffers, the exchange in front of a product
@@ -51,6 +52,7 @@ using ksd::kBlock;
 #include "ks_product.hpp"    // product of operators: generalized problems composed in HBM
 #include "ks_cheb.hpp"       // Chebyshev polynomial filter p(A): Clenshaw steps through the operator's apply_clenshaw
 #include "ks_cg.hpp"         // conjugate-gradient solve (A - theta)^-1: fused vector kernels, scalars and the stopping test on the device
+#include "ks_pcg.hpp"        // preconditioned conjugate-gradient solve with any device operator as M, the diagonal one fused; the diagonal operator
 #include "ks_minres.hpp"     // MINRES solve (A - theta)^-1 for theta inside the spectrum: the same protocol around a Lanczos recurrence
 #include "ks_bicgstab.hpp"   // BiCGStab(2) solve (A - theta)^-1 for operators that are not Hermitian: the same protocol, scalars of the operator's type
 #include "ks_grid.hpp"       // matrix-free grid operator: stencil taps in the kernel arguments plus a per-point diagonal
@@ -465,6 +467,41 @@ int ks_operator_cg_info(const ks_operator* op, int64_t* applications, int64_t* i
     if (last_iterations) *last_iterations = c->last_iterations;
     if (last_relres) *last_relres = c->last_relres;
     if (worst_relres) *worst_relres = c->worst_relres;
+  });
+}
+
+int ks_operator_diagonal(ks_ctx* ctx, int64_t n, int dtype, const double* d, ks_operator** out) {
+  return guarded([&] {
+    KS_REQUIRE(ctx && out && d, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
+    ctx->use();
+    *out = make_diagonal(ctx, n, dtype, d);
+  });
+}
+
+int ks_operator_pcg(ks_ctx* ctx, ks_operator* A, ks_operator* M, double shift, double tol, int maxit, int check_every, ks_operator** out) {
+  return guarded([&] {
+    KS_REQUIRE(ctx && out && A, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(M, KS_ERR_ARGUMENT, "ks_operator_pcg: the preconditioner is null (ks_operator_cg is the solve without one)");
+    KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, "ks_operator_pcg: single-GPU contexts only (the reductions of the solve are not summed across ranks)");
+    ctx->use();
+    *out = make_pcg(ctx, A, M, shift, tol, maxit, check_every);
+  });
+}
+
+int ks_operator_pcg_info(const ks_operator* op, int64_t* applications, int64_t* iterations, int* last_iterations, double* last_relres,
+                         double* worst_relres, int64_t* preconditioner_applications, int* path) {
+  return guarded([&] {
+    KS_REQUIRE(op, KS_ERR_ARGUMENT, "null operator");
+    const PcgOp* c = dynamic_cast<const PcgOp*>(op);
+    KS_REQUIRE(c, KS_ERR_ARGUMENT, "ks_operator_pcg_info: not an operator made by ks_operator_pcg");
+    if (applications) *applications = c->applications;
+    if (iterations) *iterations = c->iterations;
+    if (last_iterations) *last_iterations = c->last_iterations;
+    if (last_relres) *last_relres = c->last_relres;
+    if (worst_relres) *worst_relres = c->worst_relres;
+    if (preconditioner_applications) *preconditioner_applications = c->precond_applications;
+    if (path) *path = c->jacobi ? KS_PCG_PATH_JACOBI : KS_PCG_PATH_GENERIC;
   });
 }
 
@@ -1793,6 +1830,18 @@ int ks_host_cg_step(double rho, double pq, double rho_new, double stop, double* 
     if (beta) *beta = s.beta;
     if (done) *done = s.done;
     if (fail) *fail = s.fail;
+  });
+}
+
+int ks_host_pcg_step(double tau, double pq, double rho_new, double stop, double tau_new, double* alpha, double* beta, int* done, int* fail) {
+  return guarded([&] {
+    const PcgStep s = pcg_step(tau, pq, rho_new, stop);
+    PcgBeta b{0.0, 0};
+    if (!s.fail && !s.done) b = pcg_beta(tau, tau_new);
+    if (alpha) *alpha = s.alpha;
+    if (beta) *beta = b.beta;
+    if (done) *done = s.done;
+    if (fail) *fail = s.fail ? s.fail : b.fail;
   });
 }
 

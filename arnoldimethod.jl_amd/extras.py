@@ -183,6 +183,69 @@ def generalized_cg_operator(A: api.Operator, B: api.Operator, **cg) -> api.Opera
     return op
 
 
+def jacobi_preconditioner(diagonal, shift=0.0, dtype=None, ctx: api.Context | None = None) -> api.Operator:
+    """`api.diagonal_operator(1 / (diagonal - shift))`: the Jacobi preconditioner of `api.pcg_operator(A, M, shift=shift)` from the
+    matrix diagonal of A (the second value of `diffusion_terms`, `centre + potential` of a grid operator) -- what a coefficient jump
+    needs: the iteration count then follows the jump no longer.  The entries are checked here, without a device: ArgumentError
+    unless every `diagonal - shift` is positive and finite (a Hermitian positive definite A - shift I has a positive diagonal).
+    `dtype`: the element type of A, Float64 (the default) or ComplexF64; the entries stay real."""
+    d = np.asarray(diagonal)
+    if d.dtype.kind == "c":
+        if np.any(d.imag != 0):
+            raise api.ArgumentError("jacobi_preconditioner: the diagonal of a Hermitian operator is real")
+        d = d.real
+    if d.ndim != 1 or d.dtype.kind not in "fiu":
+        raise api.ArgumentError(f"jacobi_preconditioner: diagonal must be a 1-D sequence of real numbers, got shape {d.shape}, dtype {d.dtype}")
+    s = float(shift)
+    if not np.isfinite(s):
+        raise api.ArgumentError("jacobi_preconditioner: shift is not finite")
+    t = np.asarray(d, dtype=np.float64) - s
+    bad = np.flatnonzero(~(np.isfinite(t) & (t > 0)))
+    if bad.size:
+        raise api.ArgumentError(f"jacobi_preconditioner: diagonal - shift must be positive and finite, entry {int(bad[0])} is {t[bad[0]]!r} "
+                                f"({bad.size} such entries): A - shift I is not positive definite")
+    return api.diagonal_operator(1.0 / t, dtype=dtype, ctx=ctx)
+
+
+def grid_line_terms(shape, taps, potential=None, coeff=None, shift=0.0):
+    """(dl, d, du): the three central diagonals of the 3-, 5- or 7-point `api.grid_operator(shape, taps, potential)` -- with `coeff`,
+    of `api.grid_variable_operator(shape, taps, coeff, potential)` -- minus `shift` on the main one, as `tridiagonal_solve_operator`
+    takes them: the x-lines of the grid, one tridiagonal block per line.  n - 1, n and n - 1 values with n = prod(shape) and the
+    element type of the operator; `dl[r - 1]` and `du[r]` are zero where an x-line ends (ix = nx - 1), so the blocks do not touch.
+    The matrix is never formed, and the entries are the bits of `api.host_grid_matrix` / `api.host_grid_variable_matrix` on those
+    diagonals: the taps -x and +x (with `coeff`: fl(0.5 tap * fl(c[r] + c[s]))), and fl(centre + potential[r]) - shift.
+
+    The links that wrap a PERIODIC x axis are left out (they lie far from the diagonal): for such an operator the result is still a
+    valid preconditioner, the open-line part of it."""
+    dt, dims, t, v = api._grid_args(shape, taps, potential, None)
+    if np.any(dims < 1):
+        raise api.ArgumentError(f"every extent must be at least 1, shape = {shape!r}")
+    ndim, nx = int(dims.size), int(dims[0])
+    n = int(np.prod(dims))
+    s = float(shift)
+    if not np.isfinite(s):
+        raise api.ArgumentError("grid_line_terms: shift is not finite")
+    d = np.full(n, t[ndim], dtype=dt) if v is None else t[ndim] + v
+    d = d - s
+    inner = (np.arange(n - 1) % nx) != nx - 1       # row r has its +x neighbour r + 1 inside the line
+    if coeff is None:
+        lo, up = np.full(n - 1, t[ndim - 1], dtype=dt), np.full(n - 1, t[ndim + 1], dtype=dt)
+    else:
+        c = api._grid_coeff(dims, coeff)
+        pair = c[:-1] + c[1:]
+        lo, up = (0.5 * t[ndim - 1]) * pair, (0.5 * t[ndim + 1]) * pair
+    zero = np.zeros(n - 1, dtype=dt)
+    return np.where(inner, lo, zero), d, np.where(inner, up, zero)
+
+
+def line_preconditioner(shape, taps, potential=None, coeff=None, shift=0.0, ctx: api.Context | None = None) -> api.Operator:
+    """`api.tridiagonal_solve_operator(*grid_line_terms(shape, taps, potential, coeff, shift))`: the x-line preconditioner of
+    `api.pcg_operator(A, M, shift=shift)` for a grid operator whose x links dominate (an anisotropic grid, hx << hy, hz): every
+    x-line is solved exactly, 5 launches per application, and the iteration count no longer follows the anisotropy.  The lines
+    must be positive definite (they are where A - shift I is); put the strong axis first in `shape`."""
+    return api.tridiagonal_solve_operator(*grid_line_terms(shape, taps, potential, coeff, shift), ctx=ctx)
+
+
 def interior_eigenvalues(mu, shift):
     """lambda = shift + 1 / mu: the eigenvalues of A from the eigenvalues mu = 1 / (lambda - shift) of a shift-invert operator
     (`api.minres_operator(A, shift=...)`, `api.cg_operator`, `api.bicgstab_operator`, `sparse_shift_invert`) -- the

@@ -513,6 +513,40 @@ int ks_operator_bicgstab(ks_ctx* ctx, ks_operator* A, double shift_re, double sh
  * largest such residual of any solve (failed ones included).  KS_ERR_ARGUMENT for any other operator. */
 int ks_operator_bicgstab_info(const ks_operator* op, int64_t* applications, int64_t* iterations, int* last_iterations, double* last_relres,
                               double* worst_relres);
+/* (xvii) Preconditioned conjugate-gradient solve:  y ~ (A - shift I)^-1 x  for a Hermitian positive definite A - shift I, with a
+ * Hermitian positive definite device operator M ~ (A - shift I)^-1 as preconditioner -- (xiv) for the operators it cannot reach: a
+ * coefficient jump (M = the inverse diagonal, ks_operator_diagonal), an anisotropic grid (M = a line solve, (v)), incomplete factors
+ * (ks_operator_lu).  A sibling of (xiv) at every layer: the same products, record protocol, chunked host loop and determinism:
+ *     y = 0, r = x, rho0 = ||x||^2;  z = M r;  tau = Re r^H z;  p = z                 (rho0 == 0: y = 0, 0 iterations)
+ *     q = (A - shift) p;  pq = Re p^H q;  alpha = tau / pq;  r -= alpha q;  rho' = ||r||^2;  y += alpha p;
+ *     done if rho' <= tol^2 rho0  (the stopping test of (xiv): the 2-norm of the recurrence's residual, not its M-norm),
+ *     else z = M r;  tau' = Re r^H z;  beta = tau' / tau;  p = z + beta p;  tau = tau'
+ * with the scalar steps of ks_host_pcg_step.  Two paths, chosen at creation, that give the same bits:
+ *   KS_PCG_PATH_GENERIC  M is any operator: beside the product and M's own launches an iteration is four kernels that move
+ *                        16 + 24 + 16 + 40 bytes per row in Float64; the solver owns r, p, q and z.
+ *   KS_PCG_PATH_JACOBI   M was made by ks_operator_diagonal: z = d o r is formed in registers, three kernels that move 16 + 32 + 48
+ *                        bytes per row (96 against the 80 of (xiv)), no z vector.  KS_PCG_FUSED=0 forces the generic path.
+ * KS_C64 runs the same kernels on the real view.  A and M are BORROWED.  M must be the SAME linear map in every iteration: a solve of
+ * (xiv) - (xvii) as M would need flexible conjugate gradients and is refused.  A polynomial of A as M (ks_operator_chebyshev) works
+ * but does not save products.  tol, maxit and check_every as for (xiv).
+ * KS_ERR_ARGUMENT: what (xiv) refuses, and M null, made on another context, of another element type or size, or one that cannot be
+ * enqueued ahead.
+ * KS_ERR_OPERATOR at apply time, the operator staying usable: "the right-hand side is not finite", "not positive definite: p^H (A -
+ * theta) p = ... at iteration k", "the preconditioner is not positive definite: r^H M r = ... at iteration k" (not finite or <= 0;
+ * k = 0 is the start), "the residual is not finite at iteration k", "did not converge: relative residual ... after maxit iterations". */
+enum { KS_PCG_PATH_GENERIC = 0, KS_PCG_PATH_JACOBI = 1 };
+int ks_operator_pcg(ks_ctx* ctx, ks_operator* A, ks_operator* M, double shift, double tol, int maxit,
+                    int check_every /* 0: library default, 8 */, ks_operator** out);
+/* Counters of a preconditioned conjugate-gradient operator (xvii) since its creation: those of ks_operator_cg_info, the applications
+ * of M (generic path: M's launches, those behind the end of a solve inside a chunk included; Jacobi path: the times d o r was formed,
+ * one per solve and one per iteration) and the path, KS_PCG_PATH_*.  KS_ERR_ARGUMENT for any other operator. */
+int ks_operator_pcg_info(const ks_operator* op, int64_t* applications, int64_t* iterations, int* last_iterations, double* last_relres,
+                         double* worst_relres, int64_t* preconditioner_applications, int* path);
+/* (xviii) Diagonal operator:  y = d o x  with n real, finite entries d (negative ones and zeros allowed) on KS_F64 or KS_C64 vectors:
+ * a lumped mass matrix or its inverse, a scaling, the Jacobi preconditioner of (xvii).  One streaming kernel that moves 24 bytes per
+ * row in Float64; it can be enqueued ahead and is usable wherever an operator is (products, ks_vectors_apply).  d is copied.  The
+ * Newton and Clenshaw steps on it are its product and a streaming pass. */
+int ks_operator_diagonal(ks_ctx* ctx, int64_t n, int dtype, const double* d, ks_operator** out);
 int ks_operator_destroy(ks_operator* op);
 int ks_operator_size(const ks_operator* op, int64_t* n_local, int64_t* nnz, int* dtype);
 /* Device layout chosen for a stored matrix at upload (mul!(y, A, x), src/expansion.jl:121; all layouts give bit-identical y):
@@ -979,6 +1013,14 @@ int ks_host_chebyshev_plan(int degree, double center, double halfwidth, const do
  *     beta   rho_new / rho, 0 when done.
  * Any output pointer may be NULL. */
 int ks_host_cg_step(double rho, double pq, double rho_new, double stop, double* alpha, double* beta, int* done, int* fail);
+/* The scalar steps of ks_operator_pcg (xvii) without a device -- the functions its kernels run, compiled for the host: from
+ * tau = Re r^H M r, pq = Re p^H (A - theta) p, rho_new = ||r - alpha q||^2, stop = tol^2 rho0 and tau_new = Re r^H M r after the step
+ *     fail 2  pq not finite, pq <= 0, or tau / pq not finite;   fail 4  rho_new not finite:   alpha = beta = 0, done = 0;
+ *     alpha   tau / pq;     done  rho_new <= stop (rho_new == 0 is done for every stop >= 0; tau_new is then not looked at);
+ *     fail 3  not done and tau_new not finite, tau_new <= 0, or tau_new / tau not finite:   beta = 0 (alpha stands);
+ *     beta    tau_new / tau, 0 when done.
+ * (fail 1, the right-hand side is not finite, belongs to the start of a solve.)  Any output pointer may be NULL. */
+int ks_host_pcg_step(double tau, double pq, double rho_new, double stop, double tau_new, double* alpha, double* beta, int* done, int* fail);
 /* The scalar step of ks_operator_minres (xv) without a device -- the function its kernels run, compiled for the host: the new column
  * (beta, alpha, beta_new) of the Lanczos matrix through the rotations (c_prev, s_prev) and (c, s), the rotation that annihilates
  * beta_new, and the stopping test against stop = tol ||b||:
