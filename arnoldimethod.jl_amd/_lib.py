@@ -112,6 +112,8 @@ PROTOTYPES = {
     "ks_operator_pcg": [vp, vp, vp, dbl, dbl, i32, i32, P(vp)],
     "ks_operator_pcg_info": [vp, P(i64), P(i64), P(C.c_int), P(dbl), P(dbl), P(i64), P(C.c_int)],
     "ks_operator_diagonal": [vp, i64, i32, vp, P(vp)],
+    "ks_operator_multigrid": [vp, i32, P(vp), vp, P(vp), vp, vp, dbl, i32, dbl, P(vp)],
+    "ks_operator_multigrid_info": [vp, P(C.c_int), vp, P(i64), vp],
     "ks_operator_grid": [vp, i32, vp, i32, vp, vp, P(vp)],
     "ks_operator_grid_periodic": [vp, i32, vp, i32, vp, vp, vp, vp, P(vp)],
     "ks_operator_grid_star": [vp, i32, vp, i32, i32, vp, vp, P(vp)],
@@ -160,6 +162,9 @@ PROTOTYPES = {
     "ks_host_chebyshev_plan": [i32, dbl, dbl, vp, vp, P(C.c_int)],
     "ks_host_cg_step": [dbl, dbl, dbl, dbl, P(dbl), P(dbl), P(C.c_int), P(C.c_int)],
     "ks_host_pcg_step": [dbl, dbl, dbl, dbl, dbl, P(dbl), P(dbl), P(C.c_int), P(C.c_int)],
+    "ks_host_multigrid_plan": [i32, vp, P(vp), vp, i32, dbl, vp, vp, vp, vp],
+    "ks_host_multigrid_restrict": [i32, vp, vp, vp, vp, vp],
+    "ks_host_multigrid_prolong_add": [i32, vp, vp, vp, vp],
     "ks_host_minres_step": [dbl] * 9 + [vp, P(C.c_int), P(C.c_int)],
     "ks_host_bicgstab_coef": [i32, vp, vp, vp, vp, vp, vp, P(C.c_int)],
     "ks_host_bicgstab_mr": [i32, dbl, dbl, vp, vp, vp, vp, vp, P(dbl), P(C.c_int)],

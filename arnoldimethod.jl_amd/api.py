@@ -240,6 +240,18 @@ class Operator:
                     preconditioner_applications=pa.value, path="jacobi" if path.value == _lib.KS_PCG_PATH_JACOBI else "generic")
 
     @property
+    def multigrid_info(self) -> dict:
+        """Counters of a `multigrid_operator` since its creation (`ks_operator_multigrid_info`; ArgumentError for any other
+        operator): `levels`, the `rows` of every level, `applications`, `level_products` (per smoothed level the products with its
+        operator: 2 degree per application) and `coarse_applications`."""
+        n, a = C.c_int(), C.c_int64()
+        rows, prod = np.zeros(16, dtype=np.int64), np.zeros(16, dtype=np.int64)
+        check(_lib.load().ks_operator_multigrid_info(self._h, C.byref(n), rows.ctypes.data, C.byref(a), prod.ctypes.data))
+        nl = n.value
+        return dict(levels=nl, rows=tuple(int(r) for r in rows[:nl]), applications=a.value,
+                    level_products=tuple(int(p) for p in prod[:nl - 1]), coarse_applications=int(prod[nl - 1]))
+
+    @property
     def minres_info(self) -> dict:
         """Counters of a `minres_operator` since its creation (`ks_operator_minres_info`; ArgumentError for any other operator):
         solves, iterations of all of them, iterations and the recurrence's relative residual |phibar| / ||b|| of the last solve, and
@@ -648,7 +660,9 @@ def pcg_operator(A: Operator, M: Operator, shift=0.0, tol=1e-13, maxit=1000, che
     """y ~ (A - shift I)^-1 x by PRECONDITIONED conjugate gradients with the device operator M ~ (A - shift I)^-1, every vector
     resident in HBM and every scalar of the recurrence on the device (`ks_operator_pcg`): `cg_operator` for the operators it cannot
     reach -- a coefficient jump (`extras.jacobi_preconditioner`: 72 iterations where plain conjugate gradients take 519), an
-    anisotropic grid (`extras.line_preconditioner`: 16 against 94), the caller's incomplete factors (`lu_operator`).  A - shift I and M
+    anisotropic grid (`extras.line_preconditioner`: 16 against 94), a large grid (`extras.grid_multigrid_preconditioner`, a
+    `multigrid_operator`: 16 against Jacobi's 72, and a count that hardly grows with the grid), the caller's incomplete factors
+    (`lu_operator`).  A - shift I and M
     must be Hermitian positive definite and M the same linear map in every iteration; build M for A - shift I, not for A.  The
     stopping test, `tol`, `maxit` and `check_every` are `cg_operator`'s (the 2-norm of the recurrence's residual below `tol` ||x||),
     and so is the advice on an outer `partialschur`.  A `diagonal_operator` as M is fused into the solver's own kernels (three
@@ -668,6 +682,120 @@ def pcg_operator(A: Operator, M: Operator, shift=0.0, tol=1e-13, maxit=1000, che
     check(_lib.load().ks_operator_pcg(ctx._h, A._h, M._h, float(shift), float(tol), int(maxit), int(check_every), C.byref(h)))
     op = Operator(ctx, h, A.shape, A.dtype, keep=(A, M))
     op.base, op.preconditioner = A, M
+    return op
+
+
+def _mg_dims(shapes):
+    """int64[nlevels, 3]: one row of extents (x, y, z; unused axes 1) per level."""
+    try:
+        rows = [[int(e) for e in np.atleast_1d(np.asarray(s)).ravel()] for s in shapes]
+    except (TypeError, ValueError) as e:
+        raise ArgumentError(f"shapes must hold 1 to 3 integer extents per level: {shapes!r}") from e
+    if not rows or any(not 1 <= len(r) <= 3 for r in rows):
+        raise ArgumentError(f"shapes must hold 1 to 3 integer extents per level: {shapes!r}")
+    return np.ascontiguousarray([r + [1] * (3 - len(r)) for r in rows], dtype=np.int64)
+
+
+def _mg_levels(dims, inverse_diagonals, bounds):
+    """(array of pointers or None, the arrays it points to, float64 bounds) for the smoothed levels of a dims chain."""
+    nsmooth = dims.shape[0] - 1
+    lam = np.ascontiguousarray(np.atleast_1d(np.asarray(bounds, dtype=np.float64)).ravel())
+    if lam.size != nsmooth:
+        raise DimensionMismatch(f"{nsmooth} smoothed levels take {nsmooth} bounds, got {lam.size}")
+    if inverse_diagonals is None:
+        return None, [], lam
+    if len(inverse_diagonals) != nsmooth:
+        raise DimensionMismatch(f"{nsmooth} smoothed levels take {nsmooth} inverse diagonals, got {len(inverse_diagonals)}")
+    ds = []
+    for l, d in enumerate(inverse_diagonals):
+        v = np.asarray(d)
+        if v.ndim != 1 or v.dtype.kind not in "fiu":
+            raise ArgumentError(f"the inverse diagonal of level {l} must be a 1-D sequence of real numbers, got shape {v.shape}, dtype {v.dtype}")
+        if v.size != int(np.prod(dims[l])):
+            raise DimensionMismatch(f"the inverse diagonal of level {l} has {v.size} entries, its grid {tuple(int(e) for e in dims[l])} has {int(np.prod(dims[l]))}")
+        ds.append(np.ascontiguousarray(v, dtype=np.float64))
+    ptrs = (C.c_void_p * max(nsmooth, 1))(*[d.ctypes.data for d in ds])
+    return ptrs, ds, lam
+
+
+def host_multigrid_plan(shapes, bounds, degree=2, ratio=4.0, inverse_diagonals=None) -> dict:
+    """The host plan of `multigrid_operator` (`ks_host_multigrid_plan`; no device needed) for the grids `shapes` (finest first) and one
+    bound per smoothed level: `rows` per level, and per smoothed level the restriction `scale` and the Chebyshev smoother's
+    coefficients `a[l][j]`, `b[l][j]` of step j (d = a d + b dinv o (rhs - t), x += d).  Refuses what the operator refuses."""
+    dims = _mg_dims(shapes)
+    nsmooth = dims.shape[0] - 1
+    ptrs, _keep, lam = _mg_levels(dims, inverse_diagonals, bounds)
+    k = max(int(degree), 1)
+    a, b = np.zeros((max(nsmooth, 1), k)), np.zeros((max(nsmooth, 1), k))
+    scale, rows = np.zeros(max(nsmooth, 1)), np.zeros(nsmooth + 1, dtype=np.int64)
+    check(_lib.load().ks_host_multigrid_plan(nsmooth, dims.ctypes.data, ptrs, lam.ctypes.data if lam.size else None, int(degree), float(ratio),
+                                             a.ctypes.data, b.ctypes.data, scale.ctypes.data, rows.ctypes.data))
+    return dict(rows=tuple(int(r) for r in rows), scale=scale[:nsmooth].copy(), a=a[:nsmooth].copy(), b=b[:nsmooth].copy())
+
+
+def _mg_transfer_args(fine_shape, coarse_shape, *vectors):
+    dims = _mg_dims([fine_shape, coarse_shape])
+    dt = np.result_type(*[np.asarray(v).dtype for v in vectors])
+    dt = np.dtype(np.complex128 if dt.kind == "c" else np.float64)
+    return dims, dt, [np.ascontiguousarray(v, dtype=dt).ravel() for v in vectors]
+
+
+def host_multigrid_restrict(fine_shape, coarse_shape, b, t):
+    """r_c = s P^T (b - t) between two consecutive grids as `multigrid_operator`'s kernel forms it (`ks_host_multigrid_restrict`; no
+    device needed): per coarse cell the terms fl(b[i] - t[i]) of its aggregate added to +0.0 in ascending fine row order, times
+    s = 2^-(halved axes).  Float64 or ComplexF64."""
+    dims, dt, (bv, tv) = _mg_transfer_args(fine_shape, coarse_shape, b, t)
+    nf, nc = int(np.prod(dims[0])), int(np.prod(dims[1]))
+    if bv.size != nf or tv.size != nf:
+        raise DimensionMismatch(f"the fine grid {tuple(int(e) for e in dims[0])} has {nf} rows, b has {bv.size} and t {tv.size}")
+    rc = np.zeros(nc, dtype=dt)
+    check(_lib.load().ks_host_multigrid_restrict(_dtype_code(dt), dims[0].ctypes.data, dims[1].ctypes.data, bv.ctypes.data, tv.ctypes.data, rc.ctypes.data))
+    return rc
+
+
+def host_multigrid_prolong_add(fine_shape, coarse_shape, e, x):
+    """x + P e between two consecutive grids (`ks_host_multigrid_prolong_add`; no device needed): every fine cell takes the value of
+    its coarse cell.  Returns a new vector."""
+    dims, dt, (ev, xv) = _mg_transfer_args(fine_shape, coarse_shape, e, x)
+    nf, nc = int(np.prod(dims[0])), int(np.prod(dims[1]))
+    if ev.size != nc or xv.size != nf:
+        raise DimensionMismatch(f"the grids have {nf} and {nc} rows, x has {xv.size} and e {ev.size}")
+    out = xv.copy()
+    check(_lib.load().ks_host_multigrid_prolong_add(_dtype_code(dt), dims[0].ctypes.data, dims[1].ctypes.data, ev.ctypes.data, out.ctypes.data))
+    return out
+
+
+def multigrid_operator(operators, shapes, inverse_diagonals, bounds, coarse: Operator, shift=0.0, degree=2, ratio=4.0,
+                       ctx: Context | None = None) -> Operator:
+    """y = M x with M ~ (A - shift I)^-1: ONE symmetric geometric multigrid V-cycle on the grids `shapes` (finest first, len(operators)
+    + 1 of them; `ks_operator_multigrid`, csrc/ks_mg.hpp) -- a fixed Hermitian positive definite map that can be enqueued ahead, so
+    `pcg_operator(A, M, shift=shift)` takes it as its preconditioner, and usable wherever an operator is.  `operators[l]` is the
+    device operator of level l (any that can be enqueued ahead), `inverse_diagonals[l]` the real, positive 1 / (diag(A_l) - shift),
+    `bounds[l]` an upper bound on the spectrum of D_l^-1 (A_l - shift), `coarse` the operator applied on the last grid (its inverse).
+    Each smoothed level runs `degree` Chebyshev steps on [bound / ratio, bound] before and after the coarse correction; consecutive
+    grids keep or halve (ceil) each extent, the transfers are piecewise constant.  `extras.grid_multigrid_preconditioner` builds all
+    of it for -div(c grad) + V.  With no smoothed level M is `coarse`.  The cycle keeps its operators alive (`.levels`, `.coarse`);
+    closing it leaves them usable.  `.multigrid_info` counts applications and products per level."""
+    operators = list(operators)
+    for what, op in [(f"an Operator for level {l}", A) for l, A in enumerate(operators)] + [("an Operator as coarse", coarse)]:
+        if not isinstance(op, Operator):
+            raise ArgumentError(f"multigrid_operator takes {what}, got {type(op).__name__}")
+    dims = _mg_dims(shapes)
+    nsmooth = len(operators)
+    if dims.shape[0] != nsmooth + 1:
+        raise DimensionMismatch(f"{nsmooth} level operators and a coarse one take {nsmooth + 1} shapes, got {dims.shape[0]}")
+    if inverse_diagonals is None:
+        raise ArgumentError("multigrid_operator takes one inverse diagonal per smoothed level")
+    ptrs, keep, lam = _mg_levels(dims, list(inverse_diagonals), bounds)
+    ctx = ctx or coarse.ctx
+    hs = (C.c_void_p * max(nsmooth, 1))(*[A._h for A in operators])
+    h = C.c_void_p()
+    check(_lib.load().ks_operator_multigrid(ctx._h, nsmooth, hs, dims.ctypes.data, ptrs, lam.ctypes.data if lam.size else None, coarse._h,
+                                            float(shift), int(degree), float(ratio), C.byref(h)))
+    n = int(np.prod(dims[0]))
+    op = Operator(ctx, h, (n, n), coarse.dtype, keep=tuple(operators) + (coarse,))
+    op.levels, op.coarse = tuple(operators), coarse
+    del keep
     return op
 
 

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SRC = os.path.join(CSRC, "ks_hip.hip")
 BLK = os.path.join(CSRC, "ks_block_inst.hip")
-HEADERS = [os.path.join(CSRC, f) for f in ("ks_kernels.hpp", "ks_spmv_march.hpp", "ks_p2p.hpp", "ks_driver.hpp", "ks_smalldense.hpp", "ks_context.hpp", "ks_host_defs.hpp", "ks_csr_layout.hpp", "ks_halo_plan.hpp", "ks_stencil_geom.hpp", "ks_defl_plan.hpp", "ks_cheb_plan.hpp", "ks_cheb.hpp", "ks_cg_plan.hpp", "ks_cg.hpp", "ks_pcg_plan.hpp", "ks_pcg.hpp", "ks_minres_plan.hpp", "ks_minres.hpp", "ks_bicgstab_plan.hpp", "ks_bicgstab.hpp", "ks_halo.hpp", "ks_operators.hpp", "ks_sptrsv.hpp", "ks_tridiag_plan.hpp", "ks_tridiag.hpp", "ks_product.hpp", "ks_grid.hpp", "ks_grid_var.hpp", "ks_grid_box.hpp",
+HEADERS = [os.path.join(CSRC, f) for f in ("ks_kernels.hpp", "ks_spmv_march.hpp", "ks_p2p.hpp", "ks_driver.hpp", "ks_smalldense.hpp", "ks_context.hpp", "ks_host_defs.hpp", "ks_csr_layout.hpp", "ks_halo_plan.hpp", "ks_stencil_geom.hpp", "ks_defl_plan.hpp", "ks_cheb_plan.hpp", "ks_cheb.hpp", "ks_cg_plan.hpp", "ks_cg.hpp", "ks_pcg_plan.hpp", "ks_pcg.hpp", "ks_mg_plan.hpp", "ks_mg.hpp", "ks_minres_plan.hpp", "ks_minres.hpp", "ks_bicgstab_plan.hpp", "ks_bicgstab.hpp", "ks_halo.hpp", "ks_operators.hpp", "ks_sptrsv.hpp", "ks_tridiag_plan.hpp", "ks_tridiag.hpp", "ks_product.hpp", "ks_grid.hpp", "ks_grid_var.hpp", "ks_grid_box.hpp",
                                            "ks_workspace.hpp", "ks_backend.hpp", "ks_vectors.hpp", "ks_block.hpp", "ks_block_kernels.hpp", "ks_block_launch.hpp", "ks_block_mfma.hpp")]
 DEPS = [SRC, BLK] + HEADERS + [os.path.join(HERE, "..", "include", "kschur.h")]
 OUT = os.path.join(HERE, "libkschur_hip.so")

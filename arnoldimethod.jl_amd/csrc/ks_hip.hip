@@ -45,6 +45,7 @@ using ksd::kBlock;
 #include "ks_pcg_plan.hpp"     // host-only: the scalar steps of the preconditioned conjugate-gradient solve and its device record
 #include "ks_minres_plan.hpp"  // host-only: the scalar step of the MINRES solve (Lanczos column, rotations, stopping test) and its record
 #include "ks_bicgstab_plan.hpp"  // host-only: the scalar steps of the BiCGStab(2) solve (BiCG coefficients, 2 x 2 MR solve, stage tests) and its record
+#include "ks_mg_plan.hpp"      // host-only: the grids, smoother coefficients and reference transfers of the multigrid V-cycle
 #include "ks_halo.hpp"       // ... uploaded: ghost vector, transport buffers, the exchange in front of a product
 #include "ks_operators.hpp"  // ks_operator and its layouts
 #include "ks_sptrsv.hpp"     // shift-invert operator from triangular factors (sparse triangular solves)
@@ -53,6 +54,7 @@ using ksd::kBlock;
 #include "ks_cheb.hpp"       // Chebyshev polynomial filter p(A): Clenshaw steps through the operator's apply_clenshaw
 #include "ks_cg.hpp"         // conjugate-gradient solve (A - theta)^-1: fused vector kernels, scalars and the stopping test on the device
 #include "ks_pcg.hpp"        // preconditioned conjugate-gradient solve with any device operator as M, the diagonal one fused; the diagonal operator
+#include "ks_mg.hpp"         // geometric multigrid V-cycle as a fixed preconditioner: Chebyshev smoother, restriction and prolongation kernels
 #include "ks_minres.hpp"     // MINRES solve (A - theta)^-1 for theta inside the spectrum: the same protocol around a Lanczos recurrence
 #include "ks_bicgstab.hpp"   // BiCGStab(2) solve (A - theta)^-1 for operators that are not Hermitian: the same protocol, scalars of the operator's type
 #include "ks_grid.hpp"       // matrix-free grid operator: stencil taps in the kernel arguments plus a per-point diagonal
@@ -502,6 +504,31 @@ int ks_operator_pcg_info(const ks_operator* op, int64_t* applications, int64_t* 
     if (worst_relres) *worst_relres = c->worst_relres;
     if (preconditioner_applications) *preconditioner_applications = c->precond_applications;
     if (path) *path = c->jacobi ? KS_PCG_PATH_JACOBI : KS_PCG_PATH_GENERIC;
+  });
+}
+
+int ks_operator_multigrid(ks_ctx* ctx, int nsmooth, ks_operator* const* A, const int64_t* dims, const double* const* inv_diag,
+                          const double* lambda_max, ks_operator* coarse, double shift, int degree, double ratio, ks_operator** out) {
+  return guarded([&] {
+    KS_REQUIRE(ctx && out, KS_ERR_ARGUMENT, "null argument");
+    KS_REQUIRE(!ctx->distributed() && ctx->nranks == 1, KS_ERR_ARGUMENT, "ks_operator_multigrid: single-GPU contexts only (the grids are not partitioned across ranks)");
+    ctx->use();
+    *out = make_multigrid(ctx, nsmooth, A, dims, inv_diag, lambda_max, coarse, shift, degree, ratio);
+  });
+}
+
+int ks_operator_multigrid_info(const ks_operator* op, int* levels, int64_t* rows, int64_t* applications, int64_t* products) {
+  return guarded([&] {
+    KS_REQUIRE(op, KS_ERR_ARGUMENT, "null operator");
+    const MgOp* m = dynamic_cast<const MgOp*>(op);
+    KS_REQUIRE(m, KS_ERR_ARGUMENT, "ks_operator_multigrid_info: not an operator made by ks_operator_multigrid");
+    const int nl = (int)m->plan.levels.size();
+    if (levels) *levels = nl;
+    if (applications) *applications = m->applications;
+    for (int l = 0; l < nl; ++l) {
+      if (rows) rows[l] = m->plan.levels[l].rows;
+      if (products) products[l] = m->products[l];
+    }
   });
 }
 
@@ -1842,6 +1869,41 @@ int ks_host_pcg_step(double tau, double pq, double rho_new, double stop, double 
     if (beta) *beta = b.beta;
     if (done) *done = s.done;
     if (fail) *fail = s.fail ? s.fail : b.fail;
+  });
+}
+
+int ks_host_multigrid_plan(int nsmooth, const int64_t* dims, const double* const* inv_diag, const double* lambda_max, int degree, double ratio,
+                           double* a, double* b, double* scale, int64_t* rows) {
+  return guarded([&] {
+    const MgPlan P = mg_plan(nsmooth, dims, lambda_max, degree, ratio, inv_diag, "ks_host_multigrid_plan");
+    for (int l = 0; l <= nsmooth; ++l) {
+      const MgLevel& L = P.levels[l];
+      if (rows) rows[l] = L.rows;
+      if (l == nsmooth) break;
+      if (scale) scale[l] = L.scale;
+      for (int j = 0; j < degree; ++j) {
+        if (a) a[(size_t)l * degree + j] = L.a[j];
+        if (b) b[(size_t)l * degree + j] = L.b[j];
+      }
+    }
+  });
+}
+
+int ks_host_multigrid_restrict(int dtype, const int64_t* fine, const int64_t* coarse, const void* b, const void* t, void* rc) {
+  return guarded([&] {
+    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
+    KS_REQUIRE(b && t && rc, KS_ERR_ARGUMENT, "null argument");
+    const MgPair g = mg_pair(fine, coarse, "ks_host_multigrid_restrict");
+    mg_restrict_host(g, dtype == KS_F64 ? 1 : 2, static_cast<const double*>(b), static_cast<const double*>(t), static_cast<double*>(rc));
+  });
+}
+
+int ks_host_multigrid_prolong_add(int dtype, const int64_t* fine, const int64_t* coarse, const void* ec, void* x) {
+  return guarded([&] {
+    KS_REQUIRE(dtype == KS_F64 || dtype == KS_C64, KS_ERR_ARGUMENT, "unknown dtype");
+    KS_REQUIRE(ec && x, KS_ERR_ARGUMENT, "null argument");
+    const MgPair g = mg_pair(fine, coarse, "ks_host_multigrid_prolong_add");
+    mg_prolong_add_host(g, dtype == KS_F64 ? 1 : 2, static_cast<const double*>(ec), static_cast<double*>(x));
   });
 }
 

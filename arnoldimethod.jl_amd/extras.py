@@ -246,6 +246,108 @@ def line_preconditioner(shape, taps, potential=None, coeff=None, shift=0.0, ctx:
     return api.tridiagonal_solve_operator(*grid_line_terms(shape, taps, potential, coeff, shift), ctx=ctx)
 
 
+def _aggregate_mean(values, dims, halved):
+    """The arithmetic mean of a flat cell array (x fastest) over the aggregates of `multigrid_operator`: cells 2 I and 2 I + 1 along
+    every halved axis, the last cell of an odd extent alone (the true count)."""
+    a = np.asarray(values, dtype=np.float64).reshape(dims[2], dims[1], dims[0])
+    for axis, h in zip((2, 1, 0), halved):        # array axis 2 is x
+        if not h:
+            continue
+        m = a.shape[axis]
+        even, odd = np.take(a, range(0, m, 2), axis=axis), np.take(a, range(1, m, 2), axis=axis)
+        total = even.copy()
+        idx = [slice(None)] * 3
+        idx[axis] = slice(0, odd.shape[axis])
+        total[tuple(idx)] += odd
+        count = np.full(even.shape[axis], 2.0)
+        if m % 2:
+            count[-1] = 1.0
+        shape = [1, 1, 1]
+        shape[axis] = count.size
+        a = total / count.reshape(shape)
+    return np.ascontiguousarray(a.reshape(-1))
+
+
+def multigrid_hierarchy(shape, coeff, spacing=1.0, potential=None, boundary="dirichlet", shift=0.0, coarsest_rows=512):
+    """The grids of a geometric multigrid cycle for -div(c grad) + V - shift (`grid_multigrid_preconditioner`,
+    `api.multigrid_operator`): a list with one dict per level, finest first, holding `shape`, `spacing` (per axis), `coeff`,
+    `potential` (None without V), and what `diffusion_terms` makes of them -- `taps`, `diagonal` -- with `inverse_diagonal` =
+    1 / (diagonal - shift) and `bound`, an upper bound on the spectrum of D^-1 (A - shift).  Every axis with an extent of at least
+    2 is halved (ceil) from level to level until a level has at most `coarsest_rows` rows.  c and V of a coarse cell are the
+    arithmetic means over its aggregate (cells 2 I and 2 I + 1 per halved axis; the single cell of an odd tail counts once), the
+    spacing doubles on halved axes, and the coarse operator is `diffusion_terms` of those again: rediscretised, not the Galerkin
+    product.  `bound` is Gershgorin's: max_r (d_r - shift + sum |e|) / (d_r - shift), the off-diagonal sum taken from
+    `diffusion_terms(..., boundary="neumann")` without V.  ArgumentError if some d_r - shift <= 0 (A - shift I is then not positive
+    definite).  Open boundaries only.  Plain numpy, no device."""
+    s = float(shift)
+    if not np.isfinite(s):
+        raise api.ArgumentError("multigrid_hierarchy: shift is not finite")
+    if isinstance(coarsest_rows, (bool, np.bool_)) or not isinstance(coarsest_rows, (int, np.integer)) or int(coarsest_rows) < 1:
+        raise api.ArgumentError(f"multigrid_hierarchy: coarsest_rows must be a positive integer, got {coarsest_rows!r}")
+    try:
+        dims = [int(e) for e in np.atleast_1d(np.asarray(shape)).ravel()]
+    except (TypeError, ValueError) as e:
+        raise api.ArgumentError(f"shape must hold 1 to 3 integer extents: {shape!r}") from e
+    if not 1 <= len(dims) <= 3 or any(d < 1 for d in dims):
+        raise api.ArgumentError(f"a grid has 1, 2 or 3 dimensions of extent at least 1, shape = {shape!r}")
+    ndim = len(dims)
+    h = _box_spacing(ndim, spacing)
+    c = api._grid_coeff(np.asarray(dims, dtype=np.int64), coeff)
+    v = None
+    if potential is not None:
+        v = np.asarray(potential)
+        if v.dtype.kind == "c":
+            raise api.ArgumentError("multigrid_hierarchy: the potential of a Hermitian operator is real")
+        v = np.ascontiguousarray(v.reshape(-1), dtype=np.float64)
+        if v.size != c.size:
+            raise api.DimensionMismatch(f"potential must have {c.size} entries, got {v.size}")
+    levels = []
+    while True:
+        taps, diag = diffusion_terms(tuple(dims), c, h, v, boundary)
+        _, off = diffusion_terms(tuple(dims), c, h, None, "neumann")     # the sum of |e| over the links of each row
+        t = diag - s
+        bad = np.flatnonzero(~(np.isfinite(t) & (t > 0)))
+        if bad.size:
+            raise api.ArgumentError(f"multigrid_hierarchy: level {len(levels)}: diagonal - shift must be positive and finite, entry "
+                                    f"{int(bad[0])} is {t[bad[0]]!r}: A - shift I is not positive definite")
+        levels.append(dict(shape=tuple(dims), spacing=h.copy(), coeff=c, potential=v, taps=taps, diagonal=diag, inverse_diagonal=1.0 / t,
+                           bound=float(np.max((t + off) / t))))
+        halved = [1 if d >= 2 else 0 for d in dims]
+        if c.size <= int(coarsest_rows) or not any(halved):
+            return levels
+        full = dims + [1] * (3 - ndim)
+        hv = halved + [0] * (3 - ndim)
+        c = _aggregate_mean(c, full, hv)
+        v = None if v is None else _aggregate_mean(v, full, hv)
+        dims = [(d + 1) // 2 if k else d for d, k in zip(dims, halved)]
+        h = np.where(np.asarray(halved, dtype=bool), 2.0 * h, h)
+
+
+def grid_multigrid_preconditioner(shape, coeff, spacing=1.0, potential=None, boundary="dirichlet", shift=0.0, coarsest_rows=512,
+                                  degree=2, ratio=4.0, dtype=None, ctx: api.Context | None = None) -> api.Operator:
+    """The geometric multigrid preconditioner of `api.pcg_operator(A, M, shift=shift)` for A = -div(c grad) + V as
+    `diffusion_terms` / `api.grid_variable_operator` assemble it: `api.multigrid_operator` on the grids of `multigrid_hierarchy`,
+    with an `api.grid_variable_operator` per level and, on the coarsest, `api.dense_operator` of the symmetrised inverse of
+    `host_grid_variable_matrix(...) - shift I`.  Where Jacobi's iteration count doubles with the grid extent, this one's grows by a
+    few iterations; one application costs 2 `degree` products on the finest grid and about a seventh of that again below it.
+    `dtype`: the element type of A, Float64 (the default) or ComplexF64.  Open boundaries only.  The hierarchy stays readable as
+    `.hierarchy`; the cycle keeps its level operators alive."""
+    ctx = ctx or api.default_context()
+    dt = np.dtype(np.float64 if dtype is None else dtype)
+    if dt not in (np.dtype(np.float64), np.dtype(np.complex128)):
+        raise api.ArgumentError(f"element type must be float64 or complex128, not {dt}")
+    H = multigrid_hierarchy(shape, coeff, spacing, potential, boundary, shift, coarsest_rows)
+    ops = [api.grid_variable_operator(L["shape"], L["taps"], L["coeff"], L["diagonal"], dtype=dt, ctx=ctx) for L in H[:-1]]
+    last = H[-1]
+    Ac = api.host_grid_variable_matrix(last["shape"], last["taps"], last["coeff"], last["diagonal"]).toarray().real
+    inv = np.linalg.inv(Ac - float(shift) * np.eye(Ac.shape[0]))
+    coarse = api.dense_operator((0.5 * (inv + inv.T)).astype(dt), ctx)
+    M = api.multigrid_operator(ops, [L["shape"] for L in H], [L["inverse_diagonal"] for L in H[:-1]], [L["bound"] for L in H[:-1]], coarse,
+                               shift=shift, degree=degree, ratio=ratio, ctx=ctx)
+    M.hierarchy = H
+    return M
+
+
 def interior_eigenvalues(mu, shift):
     """lambda = shift + 1 / mu: the eigenvalues of A from the eigenvalues mu = 1 / (lambda - shift) of a shift-invert operator
     (`api.minres_operator(A, shift=...)`, `api.cg_operator`, `api.bicgstab_operator`, `sparse_shift_invert`) -- the

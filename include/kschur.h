@@ -547,6 +547,47 @@ int ks_operator_pcg_info(const ks_operator* op, int64_t* applications, int64_t* 
  * row in Float64; it can be enqueued ahead and is usable wherever an operator is (products, ks_vectors_apply).  d is copied.  The
  * Newton and Clenshaw steps on it are its product and a streaming pass. */
 int ks_operator_diagonal(ks_ctx* ctx, int64_t n, int dtype, const double* d, ks_operator** out);
+/* (xix) Geometric multigrid V-cycle:  y = M x  with M ~ (A_0 - shift I)^-1, ONE symmetric V-cycle on a chain of grids -- a fixed linear
+ * map, Hermitian positive definite by construction (below), that can be enqueued ahead: the preconditioner of (xvii) whose iteration
+ * count does not grow in proportion to the grid extent (generic path, unchanged), and usable wherever an operator is.  KS_F64 or
+ * KS_C64 vectors, real level data.  The cycle is generic in its level operators (any device operators that can be enqueued ahead,
+ * BORROWED like a product's factors) and geometric in its transfers.  THE DEFINITION, rounding step by rounding step (fl = one
+ * rounding to a double; the numpy model tests/mg_model.py implements the same, without the fused multiply-adds):
+ *   LEVELS  l = 0 ... L = nsmooth,  dims[3 l ...] = (nx, ny, nz) of level l, x fastest, unused axes 1, row r = ix + nx (iy + ny iz).
+ *     Per axis dims[l+1][a] is dims[l][a] (kept) or ceil(dims[l][a] / 2) (halved); at least one axis is halved per level.
+ *   AGGREGATES  coarse cell I holds the fine cells 2 I and 2 I + 1 along each halved axis; with an odd extent the last coarse cell
+ *     holds a single fine cell.
+ *   PROLONGATION  P copies the coarse value to its aggregate:  x[i] = fl(x[i] + e[I(i)]).
+ *   RESTRICTION  R = s P^T with s = 2^-(number of halved axes):  r_c[I] = s * sum fl(b[i] - t[i]) over the aggregate, the terms added
+ *     to +0.0 one by one in ascending fine row order (x fastest, then y, then z); the product by s is exact.  b - t is formed inside the
+ *     restriction kernel, t = (A_l - shift) x from the level operator's Newton step (shift == 0: its product).
+ *   SMOOTHER on l < L:  k = degree steps of the Chebyshev iteration for B = D_l^-1 (A_l - shift) on [lambda_l / ratio, lambda_l], with
+ *     dinv = inv_diag[l] (real, finite, positive) and lambda_l = lambda_max[l] an upper bound on the spectrum of B:
+ *       lo = fl(lambda / ratio);  thc = fl(fl(lambda + lo) / 2);  del = fl(fl(lambda - lo) / 2);  sig = fl(thc / del);  rho_0 = fl(1 / sig);
+ *       a_0 = 0,  b_0 = fl(1 / thc);   rho_j = fl(1 / fl(fl(2 sig) - rho_{j-1})),  a_j = fl(rho_j rho_{j-1}),  b_j = fl(fl(2 rho_j) / del);
+ *       step 0:  d = fl(b_0 fl(dinv fl(rhs - t)));                   x = fl(x + d)
+ *       step j:  d = fma(a_j, d, fl(b_j fl(dinv fl(rhs - t))));      x = fl(x + d)         with t = (A_l - shift) x before each step.
+ *     PRE-smoothing starts from x = 0: its step 0 takes rhs for rhs - t and sets x = d, so it costs k - 1 products.  POST-smoothing takes
+ *     k products and applies the same polynomial in B, which makes it the adjoint of the pre-smoother in the D-inner product: the cycle
+ *     is symmetric.  The residual polynomial is below 1 in magnitude on (0, lambda_l]: with a true upper bound and a positive definite
+ *     coarse operator the cycle is positive definite.
+ *   LEVEL L  `coarse` is applied once:  x_L = coarse b_L.
+ *   CYCLE  x = S(b);  r_c = R(b - (A - shift) x);  x += P cycle_{l+1}(r_c);  x = S(b, x):  2 k products per smoothed level.
+ * Kernels (csrc/ks_mg.hpp), bytes per row in Float64: a smoother step reads rhs, t, dinv, d, x and writes d, x (56); the restriction
+ * reads b and t and writes one coarse value per aggregate (16 + 1 in 3-D); the prolongation reads and writes x and loads one coarse
+ * value for the two fine x-cells.  No device-side decision and no host read inside the cycle; in_scale and the DevState of a batch
+ * are passed through to the level operators.  apply needs x != y.  nsmooth = 0 is allowed: M is then `coarse`.
+ * KS_ERR_ARGUMENT (the message names the level and the entry): a context of several ranks; a null operator, one made on another
+ * context, of another element type than `coarse`, or one that cannot be enqueued ahead; a size that is not the product of its level's
+ * dims; a dims chain that breaks the rule above or a level of 2^31 rows or more; more than 16 levels; degree < 1; ratio <= 1 or not
+ * finite; a lambda_max that is not finite or <= 0; an inv_diag entry that is not finite or <= 0; a shift that is not finite. */
+int ks_operator_multigrid(ks_ctx* ctx, int nsmooth, ks_operator* const* A /* nsmooth */, const int64_t* dims /* 3 (nsmooth + 1) */,
+                          const double* const* inv_diag /* nsmooth pointers to rows(l) values, copied */, const double* lambda_max /* nsmooth */,
+                          ks_operator* coarse, double shift, int degree, double ratio, ks_operator** out);
+/* Counters of a multigrid operator (xix): the number of levels nsmooth + 1, the rows of every level, the applications since creation
+ * and, per level, the products with A_l since creation (2 degree per application; the entry of the last level counts the applications
+ * of `coarse`).  rows and products have room for 16 entries.  Any output pointer may be NULL.  KS_ERR_ARGUMENT for any other operator. */
+int ks_operator_multigrid_info(const ks_operator* op, int* levels, int64_t* rows, int64_t* applications, int64_t* products);
 int ks_operator_destroy(ks_operator* op);
 int ks_operator_size(const ks_operator* op, int64_t* n_local, int64_t* nnz, int* dtype);
 /* Device layout chosen for a stored matrix at upload (mul!(y, A, x), src/expansion.jl:121; all layouts give bit-identical y):
@@ -1021,6 +1062,16 @@ int ks_host_cg_step(double rho, double pq, double rho_new, double stop, double* 
  *     beta    tau_new / tau, 0 when done.
  * (fail 1, the right-hand side is not finite, belongs to the start of a solve.)  Any output pointer may be NULL. */
 int ks_host_pcg_step(double tau, double pq, double rho_new, double stop, double tau_new, double* alpha, double* beta, int* done, int* fail);
+/* The host plan of ks_operator_multigrid (xix) without a device: the dims chain validated with that operator's refusals (inv_diag may
+ * be NULL, and so may any of its pointers: those entries are then not looked at), the rows of every level (nsmooth + 1), and per
+ * smoothed level the restriction scale s and the smoother's coefficients a[l degree + j], b[l degree + j] of step j as (xix) defines
+ * them.  Any output pointer may be NULL. */
+int ks_host_multigrid_plan(int nsmooth, const int64_t* dims /* 3 (nsmooth + 1) */, const double* const* inv_diag, const double* lambda_max,
+                           int degree, double ratio, double* a, double* b, double* scale, int64_t* rows);
+/* The reference transfers of (xix) between two consecutive levels fine[3] and coarse[3] (checked like a link of the chain), on KS_F64
+ * or KS_C64 vectors (part by part):  rc[I] = s * sum fl(b[i] - t[i])  in the order of (xix), and  x[i] = fl(x[i] + ec[I(i)]). */
+int ks_host_multigrid_restrict(int dtype, const int64_t* fine, const int64_t* coarse, const void* b, const void* t, void* rc);
+int ks_host_multigrid_prolong_add(int dtype, const int64_t* fine, const int64_t* coarse, const void* ec, void* x);
 /* The scalar step of ks_operator_minres (xv) without a device -- the function its kernels run, compiled for the host: the new column
  * (beta, alpha, beta_new) of the Lanczos matrix through the rotations (c_prev, s_prev) and (c, s), the rotation that annihilates
  * beta_new, and the stopping test against stop = tol ||b||:
