@@ -11,6 +11,13 @@ CASES: each grid is the smallest at which its kernel can still go wrong.
                  ends at extent 1
   "2d", "1d"     16 x 12 and 37 (three levels: 37 -> 19 -> 10): unused axes stay 1
   "flat-y"       6 x 1 x 4: an extent-1 axis in the middle that is never halved
+  "wide"         40 x 18 x 6, coarsest_rows = 128: 4 320 -> 540 -> 100 rows: a whole cycle whose transfers take more than one workgroup
+                 of 256 threads (restrictions: 3 with a last one of 28 threads, and 1; prolongations: 9 and 2)
+
+TRANSFER_PAIRS: the (fine, coarse) pairs on which the transfers are held bit for bit, on the host against the definition
+(tests/test_mg_model_cpu.py) and on the device against the host (tests/test_gpu_multigrid_operator.py): the first two levels of every
+case, and for each branch of k_mg_restrict / k_mg_prolong_add (csrc/ks_mg.hpp) the smallest pair that reaches it -- see the comments
+in the list.  test_mg_model_cpu.py::test_transfer_pairs_meet_the_coverage_condition computes from the shapes alone that they do.
 
 ITERATION BAND, as in tests/pcg_cases.py: `MODEL_ITS[case]` is the count of tests/pcg_model.py with the numpy cycle (tests/mg_model.py)
 as M at TOL with cg_cases.rhs, `PERMUTED_ITS` the counts with every inner product summed in a permuted row order, `SPREAD` their
@@ -39,6 +46,7 @@ CASES = {   # case -> (shape, coarsest_rows)
     "2d": ((16, 12), 64),
     "1d": ((37,), 16),
     "flat-y": ((6, 1, 4), 8),
+    "wide": ((40, 18, 6), 128),
 }
 LEVEL_SHAPES = {
     "three-level": [(12, 10, 8), (6, 5, 4), (3, 3, 2)],
@@ -48,17 +56,40 @@ LEVEL_SHAPES = {
     "2d": [(16, 12), (8, 6)],
     "1d": [(37,), (19,), (10,)],
     "flat-y": [(6, 1, 4), (3, 1, 2)],
+    "wide": [(40, 18, 6), (20, 9, 3), (10, 5, 2)],
 }
+KBLOCK = 256   # threads per workgroup of the transfer kernels: one per coarse cell (restriction), one per coarse x-cell of a fine line
+# the first two levels of every case (under the case's name: "wide" is (40, 18, 6) -> (20, 9, 3), 540 coarse rows: 3 restriction
+# workgroups, the last one of 28 threads, and 9 prolongation workgroups), then one pair per branch
+_BRANCH_PAIRS = [
+    ((45, 19, 7), (23, 10, 4)),     # 920 coarse rows; odd tails on all axes; fine lines that start at odd elements, across workgroups
+    ((70001,), (35001,)),           # 137 workgroups in 1-D, an odd tail
+    ((4096,), (2048,)),             # 8 full workgroups, aligned pairs only
+    ((12, 10, 8), (12, 5, 4)),      # x kept with extent > 1: the scalar-load branch of both kernels, `two` false on every thread
+    ((12, 10, 8), (6, 10, 4)),      # y kept
+    ((12, 10, 8), (6, 5, 8)),       # z kept
+    ((13, 6, 5), (13, 3, 5)),       # one halved axis only (s = 1/2); x kept and odd
+    ((5, 4), (5, 2)),
+    ((2, 9, 5), (1, 5, 3)),         # nxc = 1 from a halved x
+    ((1, 64, 3), (1, 32, 2)),       # x of extent 1 next to halved y and z
+    ((31, 12, 7), (16, 6, 4)),      # mixed parity
+    ((6, 5, 4), (3, 3, 2)),         # the second-level pairs of "three-level" and "1d"
+    ((19,), (10,)),
+]
+TRANSFER_PAIRS = [(s[0], s[1]) for s in LEVEL_SHAPES.values()] + _BRANCH_PAIRS
+TRANSFER_IDS = list(LEVEL_SHAPES) + ["x".join(map(str, f)) + "-" + "x".join(map(str, c)) for f, c in _BRANCH_PAIRS]
 PERMUTATION_SEEDS = pc.PERMUTATION_SEEDS
 
 # recorded on a CPU (numpy 2.x); recomputed and printed by tests/test_mg_model_cpu.py
-MODEL_ITS = {"two-level": 16, "three-level": 16}           # (Jacobi: pcg_cases.MODEL_ITS["jump"] = 72)
-PERMUTED_ITS = {"two-level": (16,) * 6, "three-level": (16,) * 6}   # measured spread: 0 and 0
-HARD_ITS = {"two-level": 16, "three-level": 17}            # the same with a jump of 1e4 in c
-SHIFTED_ITS = {"two-level": 14, "three-level": 15}         # shift = -1
+# (Jacobi: pcg_cases.MODEL_ITS["jump"] = 72 on 12 x 10 x 8; on the grid of "wide" the model of Jacobi takes 99, and 91 at shift = -1)
+MODEL_ITS = {"two-level": 16, "three-level": 16, "wide": 19}
+PERMUTED_ITS = {"two-level": (16,) * 6, "three-level": (16,) * 6, "wide": (19,) * 6}   # measured spread: 0, 0 and 0
+HARD_ITS = {"two-level": 16, "three-level": 17, "wide": 20}           # the same with a jump of 1e4 in c
+SHIFTED_ITS = {"two-level": 14, "three-level": 15, "wide": 16}        # shift = -1
 SPREAD = {case: max(v) - min(v) for case, v in PERMUTED_ITS.items()}
 # the larger of the Float64 and the ComplexF64 figure
-ERR = {"three-level": 2.43e-16, "two-level": 2.39e-16, "odd": 2.61e-16, "long-x": 2.38e-16, "2d": 1.72e-16, "1d": 1.88e-16, "flat-y": 1.63e-16}
+ERR = {"three-level": 2.43e-16, "two-level": 2.39e-16, "odd": 2.61e-16, "long-x": 2.38e-16, "2d": 1.72e-16, "1d": 1.88e-16, "flat-y": 1.63e-16,
+       "wide": 2.53e-16}
 
 
 def band(case):

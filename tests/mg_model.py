@@ -66,15 +66,37 @@ def prolong(fine, coarse, e):
     return E[np.ix_(iz, iy, ix)].reshape(-1)
 
 
+class Diagonals:
+    """A scipy sparse matrix held by its stored diagonals in the precision of `real`, so that a product in np.longdouble needs no
+    dense copy (7 diagonals of a stencil instead of n^2 entries).  `D @ x` adds the terms of a row in ascending column order, which
+    is the order of numpy's own np.longdouble matrix product; the zeros that one adds in between change no bit."""
+
+    def __init__(self, matrix, real):
+        dia = matrix.todia()
+        self.n = dia.shape[0]
+        assert dia.shape == (self.n, self.n)
+        order = np.argsort(dia.offsets)
+        self.offsets = [int(o) for o in dia.offsets[order]]
+        self.data = np.asarray(dia.data)[order].astype(real)     # data[k, j] = A[j - offsets[k], j]
+
+    def __matmul__(self, x):
+        y = np.zeros(self.n, dtype=np.result_type(self.data.dtype, x.dtype))
+        for off, d in zip(self.offsets, self.data):
+            lo, hi = max(off, 0), min(self.n + off, self.n)      # the columns j of this diagonal; its rows are j - off
+            y[lo - off:hi - off] += d[lo:hi] * x[lo:hi]
+        return y
+
+
 class Cycle:
     """M as a callable b -> M b.  `matrices[l]`: the level matrices (dense or scipy sparse, real); `inverse_diagonals[l]`,
-    `bounds[l]`; `coarse`: the dense matrix applied on the last level."""
+    `bounds[l]`; `coarse`: the dense matrix applied on the last level.  In a wider precision than Float64 a sparse level matrix is
+    held as `Diagonals`, a dense one as a dense copy."""
 
     def __init__(self, matrices, shapes, inverse_diagonals, bounds, coarse, shift=0.0, degree=2, ratio=4.0, real=np.float64):
         assert len(shapes) == len(matrices) + 1 == len(inverse_diagonals) + 1 == len(bounds) + 1
         self.real, self.degree, self.shapes = real, int(degree), [tuple(np.atleast_1d(s)) for s in shapes]
         wide = real is not np.float64
-        self.A = [np.asarray(m.toarray() if hasattr(m, "toarray") else m).astype(real) if wide else m for m in matrices]
+        self.A = [(Diagonals(m, real) if hasattr(m, "todia") else np.asarray(m).astype(real)) if wide else m for m in matrices]
         self.dinv = [np.asarray(d).astype(real) for d in inverse_diagonals]
         self.coarse = np.asarray(coarse).astype(real) if wide else np.asarray(coarse)
         self.shift = real(shift)

@@ -74,14 +74,15 @@ def _scale(d, v):
 # ------------------------------------------------------------------------------------------------ 1. the transfers alone
 @pytest.mark.parametrize("variant", ["restriction-alone", "whole-cycle"])
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
-@pytest.mark.parametrize("case", list(cases.CASES))
-def test_transfers_carry_the_bits_of_the_host_functions(case, dtype, variant, ctx):
+@pytest.mark.parametrize("fine,coarse", cases.TRANSFER_PAIRS, ids=cases.TRANSFER_IDS)
+def test_transfers_carry_the_bits_of_the_host_functions(fine, coarse, dtype, variant, ctx):
     """Two levels, degree 1, diagonal operators on both: every step of the cycle is one individually rounded operation per entry, so
     numpy and the host transfers reproduce the device bit for bit --
         x1 = b0 (dinv o b);  r_c = R(b - a o x1);  x2 = x1 + P (e o r_c);  y = x2 + b0 (dinv o (b - a o x2)).
     "restriction-alone": dinv = 2^-200 and e = 1 make x1 and the post-smoothing step vanish against P r_c: y holds the very bits of
-    the coarse right-hand side, prolonged."""
-    fine, coarse = cases.LEVEL_SHAPES[case][:2]
+    the coarse right-hand side, prolonged -- every coarse cell of every workgroup of the restriction is seen on its fine rows.
+    On mg_cases.TRANSFER_PAIRS: the first two levels of every case and one pair per branch of the two kernels (workgroups past the
+    first, kept axes, a single coarse x-cell, unaligned lines), as tests/test_mg_model_cpu.py computes from the shapes."""
     nf, nc = cc.size(fine), cc.size(coarse)
     rng = np.random.default_rng(nf)
     a = 0.5 + rng.random(nf)
@@ -105,6 +106,58 @@ def test_transfers_carry_the_bits_of_the_host_functions(case, dtype, variant, ct
         assert np.array_equal(_bits(y), _bits(pkg.host_multigrid_prolong_add(fine, coarse, rc, np.zeros(nf, dtype=dtype))))
     info = M.multigrid_info
     assert info == dict(levels=2, rows=(nf, nc), applications=1, level_products=(2,), coarse_applications=1), info
+
+
+def _diagonal_chain(shapes, a, dinv, b0, e, b, l=0):
+    """cycle_l(b) of a chain of diagonal levels at degree 1, every operation rounded once in the order of the device:
+        l == L: e o b;  x1 = b0_l (dinv_l o b);  r_c = R(b - a_l o x1);  x2 = x1 + P cycle_{l+1}(r_c);  x2 + b0_l (dinv_l o (b - a_l o x2))."""
+    if l == len(shapes) - 1:
+        return _scale(e, b)
+    x1 = b0[l] * _scale(dinv[l], b)
+    rc = pkg.host_multigrid_restrict(shapes[l], shapes[l + 1], b, _scale(a[l], x1))
+    x2 = pkg.host_multigrid_prolong_add(shapes[l], shapes[l + 1], _diagonal_chain(shapes, a, dinv, b0, e, rc, l + 1), x1)
+    return x2 + b0[l] * _scale(dinv[l], b - _scale(a[l], x2))
+
+
+_HALVINGS = [(2 ** k + 1,) for k in range(15, 0, -1)] + [(2,)]     # 32769 -> 16385 -> ... -> 3 -> 2: the 16 levels the plan accepts
+CHAINS = {
+    # 2 604 and 384 coarse rows: 11 and 2 restriction workgroups, each with a partial last one, on levels of mixed parity
+    "three-3d": [(61, 23, 13), (31, 12, 7), (16, 6, 4)],
+    # y kept, then z kept: the kept and the halved axes change from level to level
+    "kept-then-halved": [(45, 19, 7), (23, 19, 4), (12, 10, 4)],
+    "sixteen-1d": _HALVINGS,
+}
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("chain", list(CHAINS))
+def test_a_chain_of_diagonal_levels_carries_the_bits_of_the_recursion(chain, dtype, ctx):
+    """The two-level closed form of test_transfers_carry_the_bits_of_the_host_functions, recursively: degree 1 and a diagonal operator
+    on every level, so numpy and the host transfers reproduce the device bit for bit at any depth.  Unlike the whole-cycle tests
+    this holds the right-hand sides and solutions of the levels l >= 1 (rhs[l + 1], sol[l + 1] of csrc/ks_mg.hpp) to the bit: a
+    wrong value in any of them reaches y through the prolongations.  Each level has a bound of its own, so a coefficient taken from
+    another level shows.  The second application runs on temporaries the first one has written."""
+    shapes = CHAINS[chain]
+    rows = [cc.size(s) for s in shapes]
+    L = len(shapes) - 1
+    rng = np.random.default_rng(rows[0])
+    a = [0.5 + rng.random(n) for n in rows[:-1]]
+    dinv = [(0.5 + rng.random(n)) / a[l] for l, n in enumerate(rows[:-1])]
+    e = 0.5 + rng.random(rows[-1])
+    bounds = [1.0 + 0.125 * l for l in range(L)]
+    b0 = pkg.host_multigrid_plan(shapes, bounds, degree=1, ratio=4.0)["b"][:, 0]
+    assert len(set(b0)) == L
+    M = pkg.multigrid_operator([pkg.diagonal_operator(v, dtype, ctx) for v in a], shapes, dinv, bounds, pkg.diagonal_operator(e, dtype, ctx),
+                               degree=1, ratio=4.0)
+    b = cc.rhs(rows[0], dtype)
+    want = _diagonal_chain(shapes, a, dinv, b0, e, b).astype(dtype)
+    assert np.all(np.isfinite(want.view(np.float64))) and np.all(want.view(np.float64) != 0.0)
+    solve = Solver(M)
+    y = solve(b)
+    assert np.array_equal(_bits(y), _bits(want)), np.abs(y - want).max()
+    assert M.multigrid_info == dict(levels=L + 1, rows=tuple(rows), applications=1, level_products=(2,) * L, coarse_applications=1)
+    assert np.array_equal(_bits(solve(b)), _bits(want))
+    assert M.multigrid_info == dict(levels=L + 1, rows=tuple(rows), applications=2, level_products=(4,) * L, coarse_applications=2)
 
 
 # ------------------------------------------------------------------------------------------------ 2. the smoother in closed form
@@ -167,13 +220,42 @@ def _case(case, shift=0.0, jump=cases.JUMP):
     return cases.setup(pkg, extras, case, jump=jump, shift=shift)
 
 
-def _device_cycle(case, dtype, ctx, shift=0.0, degree=cases.DEGREE, ratio=cases.RATIO, bound_factor=1.0, jump=cases.JUMP):
+def _device_cycle(case, dtype, ctx, shift=0.0, degree=cases.DEGREE, ratio=cases.RATIO, bound_factor=1.0, jump=cases.JUMP, stored=False):
+    """`stored`: the level operators are the stored matrices `csr_operator(mats[l])` instead of the matrix-free grid operators."""
     H, mats, coarse = _case(case, shift, jump)
-    ops = [pkg.grid_variable_operator(L["shape"], L["taps"], L["coeff"], L["diagonal"], dtype=dtype, ctx=ctx) for L in H[:-1]]
+    if stored:
+        ops = [pkg.csr_operator(m.astype(dtype), ctx) for m in mats[:-1]]
+    else:
+        ops = [pkg.grid_variable_operator(L["shape"], L["taps"], L["coeff"], L["diagonal"], dtype=dtype, ctx=ctx) for L in H[:-1]]
     M = pkg.multigrid_operator(ops, [L["shape"] for L in H], [L["inverse_diagonal"] for L in H[:-1]], [bound_factor * L["bound"] for L in H[:-1]],
                                pkg.dense_operator(coarse.astype(dtype), ctx), shift=shift, degree=degree, ratio=ratio)
     assert M.levels == tuple(ops) and M.dtype == np.dtype(dtype)
     return M, ops[0]
+
+
+@functools.lru_cache(maxsize=None)
+def _exact_cycle(case, dtype):
+    """(b, M b of the numpy model in np.longdouble, M b of the Float64 model): computed once, read only."""
+    H, mats, coarse = _case(case)
+    b = cases.rhs(case, dtype)
+    out = b, cases.model(H, mats, coarse, real=np.longdouble)(b), cases.model(H, mats, coarse)(b)
+    for v in out:
+        v.setflags(write=False)
+    return out
+
+
+def _check_whole_cycle(case, dtype, ctx, stored):
+    M, _ = _device_cycle(case, dtype, ctx, stored=stored)
+    b, exact, model = _exact_cycle(case, dtype)
+    y = Solver(M)(b)
+    err, err_model = cases.rel_err(y, exact), cases.rel_err(model, exact)
+    print("%s %s%s: device %.3g, Float64 model %.3g, ERR %.3g, allowed %.3g"
+          % (case, np.dtype(dtype).name, ", stored matrices" if stored else "", err, err_model, cases.ERR[case], 4 * cases.ERR[case]))
+    assert np.all(np.isfinite(y))
+    assert err <= 4 * cases.ERR[case], (err, cases.ERR[case])
+    info = M.multigrid_info
+    assert info["rows"] == tuple(cc.size(s) for s in cases.LEVEL_SHAPES[case])
+    assert info["level_products"] == (2 * cases.DEGREE,) * (len(cases.LEVEL_SHAPES[case]) - 1)
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
@@ -181,17 +263,15 @@ def _device_cycle(case, dtype, ctx, shift=0.0, degree=cases.DEGREE, ratio=cases.
 def test_whole_cycle_against_the_model(case, dtype, ctx):
     """M b against the numpy model evaluated in np.longdouble: the Float64 model lies ERR[case] from it (mg_cases), the device may
     lie 4 ERR from it."""
-    H, mats, coarse = _case(case)
-    M, _ = _device_cycle(case, dtype, ctx)
-    b = cases.rhs(case, dtype)
-    y = Solver(M)(b)
-    exact = cases.model(H, mats, coarse, real=np.longdouble)(b)
-    err, err_model = cases.rel_err(y, exact), cases.rel_err(cases.model(H, mats, coarse)(b), exact)
-    print("%s %s: device %.3g, Float64 model %.3g, ERR %.3g, allowed %.3g" % (case, np.dtype(dtype).name, err, err_model, cases.ERR[case], 4 * cases.ERR[case]))
-    assert np.all(np.isfinite(y))
-    assert err <= 4 * cases.ERR[case], (err, cases.ERR[case])
-    info = M.multigrid_info
-    assert info["rows"] == tuple(cc.size(s) for s in cases.LEVEL_SHAPES[case]) and info["level_products"] == (2 * cases.DEGREE,) * (len(H) - 1)
+    _check_whole_cycle(case, dtype, ctx, stored=False)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("case", ["three-level", "wide"])
+def test_whole_cycle_with_stored_matrices_as_level_operators(case, dtype, ctx):
+    """The cycle is generic in its level operators: the same matrices as `csr_operator`s give the same map with another order of the
+    sums inside a product, so the same bound of 4 ERR holds."""
+    _check_whole_cycle(case, dtype, ctx, stored=True)
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)

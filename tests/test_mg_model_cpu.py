@@ -19,6 +19,7 @@ from arnoldimethod_jl_amd import extras  # noqa: E402
 
 EPS = np.finfo(np.float64).eps
 PAIRS = [(s[0], s[1]) for s in cases.LEVEL_SHAPES.values()] + [((37,), (19,)), ((19,), (10,)), ((6, 5, 4), (3, 3, 2)), ((5, 4), (5, 2))]
+PAIRS += [p for p in cases.TRANSFER_PAIRS if p not in PAIRS]     # every pair the device is held to the host functions on
 DTYPES = [np.float64, np.complex128]
 IDS = ["f64", "c64"]
 
@@ -171,6 +172,33 @@ def test_restriction_is_the_scaled_adjoint_of_the_prolongation(fine, coarse):
     Rv = pkg.host_multigrid_restrict(fine, coarse, v, np.zeros(nf))
     Pw = pkg.host_multigrid_prolong_add(fine, coarse, w, np.zeros(nf))
     assert np.dot(Rv, w) == s * np.dot(v, Pw)
+
+
+def test_transfer_pairs_meet_the_coverage_condition():
+    """TRANSFER_PAIRS reaches every branch of k_mg_restrict (one thread per coarse cell) and k_mg_prolong_add (one thread per coarse
+    x-cell of a fine line), 256 threads per workgroup -- computed from the shapes, so that a change of shapes cannot lose a branch
+    silently: workgroups past the first two with a partial last one, each axis kept with an extent above 1 (x kept: the scalar
+    accesses with a single cell per thread), a single coarse x-cell, fine lines that start at odd elements (odd nxf, more than one
+    line), and a scale of 1/2."""
+    assert cases.KBLOCK == 256 and len(cases.TRANSFER_IDS) == len(cases.TRANSFER_PAIRS) == len(set(cases.TRANSFER_IDS))
+    assert cases.TRANSFER_PAIRS[:len(cases.LEVEL_SHAPES)] == [(s[0], s[1]) for s in cases.LEVEL_SHAPES.values()]
+    for p in [((6, 5, 4), (3, 3, 2)), ((19,), (10,))]:                # the second-level pairs of the hierarchies
+        assert p in cases.TRANSFER_PAIRS and p in [(s[1], s[2]) for s in cases.LEVEL_SHAPES.values() if len(s) > 2]
+    geo = [(model.dims3(f), model.dims3(c), model.halved(f, c)) for f, c in cases.TRANSFER_PAIRS]
+
+    def blocks(threads):
+        return -(-threads // cases.KBLOCK)
+
+    assert any(blocks(c[0] * c[1] * c[2]) >= 3 and (c[0] * c[1] * c[2]) % cases.KBLOCK != 0 for f, c, h in geo)
+    assert any(blocks(c[0] * f[1] * f[2]) >= 3 for f, c, h in geo)
+    for axis in range(3):
+        assert any(not h[axis] and f[axis] > 1 for f, c, h in geo), axis
+    assert any(c[0] == 1 and h[0] for f, c, h in geo) and any(c[0] == 1 and not h[0] for f, c, h in geo)
+    assert any(f[0] % 2 == 1 and f[1] * f[2] > 1 and h[0] for f, c, h in geo)
+    assert any(sum(h) == 1 for f, c, h in geo)
+    assert any(len({e % 2 for e in f}) == 2 and all(h) for f, c, h in geo)      # mixed parity with every axis halved
+    print("restriction workgroups %s, prolongation workgroups %s"
+          % ([blocks(c[0] * c[1] * c[2]) for f, c, h in geo], [blocks(c[0] * f[1] * f[2]) for f, c, h in geo]))
 
 
 def test_transfers_refuse_grids_that_are_not_consecutive():
